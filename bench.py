@@ -18,6 +18,9 @@ Second measured leg (`rollout` in the line; BASELINE config #3, R:src/r1-v/src/o
 rank r takes prompt r, samples G = 8 completions (top_p 0.95, T 1) behind one ViT pass and one prefill, computes their
 per-token log-probs and the rewards, and the ranks exchange the packed [G, 9+] record with ONE all_gather_into_tensor
 per step (RCCL over xGMI when the backend is nccl) -- the collective is inside the timed region.
+
+`--dump-outputs DIR`: after the timed steps, rank 0 writes what the last timed step returned to its caller as DIR/<name>.npy
+(float64).  Prompt, frames and weights are all seeded, so two builds run with the same arguments can be compared file for file.
 """
 from __future__ import annotations
 
@@ -295,6 +298,13 @@ def rollout_leg(cfg, eng, ids, pixel_values, grid, dist, dev, G=8, T=768, steps=
             "backend": dist.get_backend() if dist else None}
 
 
+def dump_outputs(dirname, out):
+    """The headline step's GenerateOutput holds one array, `sequences` (i64 [1, S + new_tokens]; margins are not requested),
+    written as float64, in which token ids are exact."""
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "sequences.npy"), out.sequences.cpu().numpy().astype(np.float64))
+
+
 def launch_check():
     """CPU-only check of the launch path (tests/test_bench_launch_cpu.py): join the world over gloo, run the rollout's
     metrics collective on a dummy record, let rank 0 print the world size."""
@@ -328,7 +338,10 @@ def main():
     ap.add_argument("--rollout-tokens", type=int, default=768)
     ap.add_argument("--launch-check", action="store_true", help="CPU-only: join the world over gloo and print its size")
     ap.add_argument("--no-fp8", action="store_true", help="skip the extra fp8-weight decode measurement")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world_env = os.environ.get("WORLD_SIZE")
     if world_env is None and args.gpus > 1:
@@ -425,6 +438,8 @@ def main():
     torch.cuda.synchronize()
     dt = reduce_max(time.perf_counter() - t0)
     assert out.sequences.shape[1] == S + args.new_tokens
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
 
     # per-stage breakdown (one extra, untimed, synchronised step)
     stages = step(0, timings=True).timings

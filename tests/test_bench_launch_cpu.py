@@ -39,6 +39,12 @@ def test_world_size_mismatch_is_an_error():
     assert not [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
 
 
+def test_zero_timed_steps_is_an_error():
+    r = _run(["--gpus", "1", "--steps", "0"])
+    assert r.returncode != 0 and "--steps" in r.stderr
+    assert not [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+
+
 def test_failing_rank_fails_the_launch(tmp_path):
     from open_o3_video_amd.launch import spawn_ranks
     script = tmp_path / "w.py"
