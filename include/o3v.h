@@ -303,6 +303,36 @@ int o3v_mark_seen(const int* ids, void* seen, int B, int S, int V, o3v_stream_t 
 /* _get_per_token_logps, R:grpo_trainer.py:371-384: out[r] = log_softmax(logits[r])[target[r]] */
 int o3v_logprob_gather(const void* logits, const int* target, float* out, int R, int V, int ldl, o3v_stream_t stream);
 
+/* Top-N log-probs, vLLM 0.7.2 SamplingParams(logprobs=N, prompt_logprobs=N) with the V0 sampler's semantics: log-probs of the
+ * PROCESSED distribution a token was drawn from (vllm/model_executor/layers/sampler.py _get_logprobs; parity unpinned).
+ * Processed scores: repetition penalty from the seen map as it was before the step (TF:logits_process.py:404-414), temperature
+ * (:301-303), then for sampling rows the top-k (:590-594) and top-p (:527-539) masks, masked tokens at -inf and the kept ones
+ * renormalised over the kept mass the draw used.  Greedy rows: penalty only, temperature 1.
+ *   chosen_lp   log-prob of the emitted token;  chosen_rank  1 + number of tokens with a strictly larger processed log-prob
+ *   top_ids / top_lp  the n largest processed log-probs, descending, ties to the lower token id; when fewer than n tokens survive
+ *   the masks the rest follow at -inf, lowest ids first (-1 past the vocabulary) */
+#define O3V_MAX_LOGPROBS 20 /* vLLM's default max_logprobs */
+typedef struct {
+    int n;                /* top entries per position, 0..O3V_MAX_LOGPROBS */
+    float *chosen_lp;     /* f32 [B, Tnew] */
+    int *chosen_rank;     /* i32 [B, Tnew] */
+    int *top_ids;         /* i32 [B, Tnew, n] (may be NULL when n == 0) */
+    float *top_lp;        /* f32 [B, Tnew, n] */
+} o3v_logprob_opts;
+/* One decode step as o3v_llm_decode_lp runs it: the sampler (do_sample 0: o3v_sample_greedy, 1: o3v_sample_top_k_top_p; same ids,
+ * same seen / finished / margins updates), then the log-probs of that step into lp's arrays at column `step` (row stride out_stride).
+ * B <= 32; scratch: f32 [B * O3V_SAMPLE_SCRATCH_FLOATS] in both modes, 8-byte aligned. */
+int o3v_sample_logprobs(const void* logits, void* seen, int* cur_tok, int* finished, int* out_ids, float* margins,
+                        const int* eos_ids, int n_eos, int pad_id, int B, int V, int ldl, int do_sample, float rep_penalty,
+                        float temperature, int top_k, float top_p, uint64_t seed, const int* row_id, int step, int out_stride,
+                        float* scratch, const o3v_logprob_opts* lp, o3v_stream_t stream);
+/* Prompt side (vLLM prompt_logprobs; R:grpo_trainer.py:371-384 for the target log-prob): the same selection on raw logits (no
+ * penalty, temperature 1, no masks) of R <= 65535 rows; row r predicts target[r].  Outputs [R] and [R, n]. */
+#define O3V_LOGPROB_ROW_SCRATCH_FLOATS 384 /* per row */
+int o3v_logprobs_rows(const void* logits, const int* target, int R, int V, int ldl, int n, float* target_lp, int* target_rank,
+                      int* top_ids, float* top_lp, float* scratch /* f32 [R * O3V_LOGPROB_ROW_SCRATCH_FLOATS] */,
+                      o3v_stream_t stream);
+
 /* ---- model-level engine (layer loops in C++, no Python per kernel) ------------------------------------------- */
 typedef struct {
     const void *norm1, *norm2;     /* [hid] */
@@ -488,6 +518,11 @@ typedef struct {
  * st->logits, then (unless it is the globally last step) run one decode forward to refill st->logits. */
 int o3v_llm_decode(const o3v_llm_desc* d, const o3v_decode_state* st, int step0, int n_steps, int skip_last_forward,
                    o3v_stream_t stream);
+/* The same with the log-probs of every emitted token (vLLM SamplingParams.logprobs, see o3v_logprob_opts): lp == NULL is
+ * o3v_llm_decode exactly (same launches, same ids).  Otherwise each step adds the two log-prob launches after the sampler, and
+ * st->sample_scratch must hold O3V_SAMPLE_SCRATCH_FLOATS per row in greedy mode as well; B <= 32. */
+int o3v_llm_decode_lp(const o3v_llm_desc* d, const o3v_decode_state* st, const o3v_logprob_opts* lp, int step0, int n_steps,
+                      int skip_last_forward, o3v_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -160,3 +160,15 @@ inline thread_local long long o3v_tl_launches = 0;  // (C++17 inline variable: o
         hipError_t e__ = hipGetLastError();                 \
         if (e__ != hipSuccess) return O3V_ERR_LAUNCH;       \
     } while (0)
+
+// ---- entry points shared between translation units (C++ linkage, not part of include/o3v.h)
+// samplers with an optional u8 [B] `seen_prev`: the chosen token's seen byte before the step sets it (the log-prob pass needs the
+// repetition-penalty state the token was drawn under)
+int o3v_sample_greedy_ex(const void* logits, void* seen, int* cur_tok, int* finished, int* out_ids, float* margins,
+                         const int* eos_ids, int n_eos, int pad_id, int B, int V, int ldl, float rep_penalty, int step,
+                         int out_stride, float* scratch, const void* embed, void* x_out, int hidden, uint8_t* seen_prev,
+                         hipStream_t stream);
+int o3v_sample_top_k_top_p_ex(const void* logits, void* seen, int* cur_tok, int* finished, int* out_ids, float* chosen_logprob,
+                               const int* eos_ids, int n_eos, int pad_id, int B, int V, int ldl, float rep_penalty, float temperature,
+                               int top_k, float top_p, uint64_t seed, const int* row_id, int step, int out_stride, float* scratch,
+                               uint8_t* seen_prev, hipStream_t stream);

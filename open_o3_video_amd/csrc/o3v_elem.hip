@@ -741,7 +741,7 @@ __global__ __launch_bounds__(64) void sample_greedy_final_kernel(const float* __
                                                                  const int* __restrict__ eos_ids, int n_eos, int pad_id,
                                                                  int V, int step, int out_stride,
                                                                  const uint4* __restrict__ embed, uint4* __restrict__ x_out,
-                                                                 int hidden) {
+                                                                 int hidden, uint8_t* __restrict__ seen_prev) {
     const int b = blockIdx.x, lane = threadIdx.x;
     const float* p = part + ((size_t)b * GREEDY_NB + lane) * 4;
     float best = -INFINITY, second = -INFINITY;
@@ -763,6 +763,7 @@ __global__ __launch_bounds__(64) void sample_greedy_final_kernel(const float* __
             for (int k = 0; k < n_eos; ++k)
                 if (tok == eos_ids[k]) finished[b] = 1;
         }
+        if (seen_prev) seen_prev[b] = (tok >= 0 && tok < V) ? seen[(size_t)b * V + tok] : 0;  // log-probs see the map before this step
         if (tok >= 0 && tok < V) seen[(size_t)b * V + tok] = 1;
         cur_tok[b] = tok;
         out_ids[(size_t)b * out_stride + step] = tok;
@@ -777,10 +778,11 @@ __global__ __launch_bounds__(64) void sample_greedy_final_kernel(const float* __
     }
 }
 
-// scratch: f32 [B, 64, 4] partials
-static int sample_greedy_impl(const void* logits, void* seen, int* cur_tok, int* finished, int* out_ids, float* margins,
-                              const int* eos_ids, int n_eos, int pad_id, int B, int V, int ldl, float rep_penalty, int step,
-                              int out_stride, float* scratch, const void* embed, void* x_out, int hidden, hipStream_t stream) {
+// scratch: f32 [B, 64, 4] partials.  seen_prev (optional, u8 [B]): the chosen token's seen byte before this step sets it
+int o3v_sample_greedy_ex(const void* logits, void* seen, int* cur_tok, int* finished, int* out_ids, float* margins,
+                         const int* eos_ids, int n_eos, int pad_id, int B, int V, int ldl, float rep_penalty, int step,
+                         int out_stride, float* scratch, const void* embed, void* x_out, int hidden, uint8_t* seen_prev,
+                         hipStream_t stream) {
     if (!logits || !seen || !cur_tok || !finished || !out_ids || !scratch || B < 0 || V <= 0 || step < 0 ||
         step >= out_stride)
         return O3V_ERR_ARG;
@@ -789,7 +791,7 @@ static int sample_greedy_impl(const void* logits, void* seen, int* cur_tok, int*
     O3V_KLAUNCH(sample_greedy_partial_kernel, dim3(GREEDY_NB, B), dim3(256), 0, stream, (const bf16_t*)logits,
                 (const uint8_t*)seen, scratch, V, ldl, rep_penalty);
     O3V_KLAUNCH(sample_greedy_final_kernel, dim3(B), dim3(64), 0, stream, scratch, (uint8_t*)seen, cur_tok, finished, out_ids,
-                margins, eos_ids, n_eos, pad_id, V, step, out_stride, (const uint4*)embed, (uint4*)x_out, hidden);
+                margins, eos_ids, n_eos, pad_id, V, step, out_stride, (const uint4*)embed, (uint4*)x_out, hidden, seen_prev);
     O3V_CHECK_LAUNCH();
     return O3V_OK;
 }
@@ -797,8 +799,8 @@ static int sample_greedy_impl(const void* logits, void* seen, int* cur_tok, int*
 extern "C" int o3v_sample_greedy(const void* logits, void* seen, int* cur_tok, int* finished, int* out_ids, float* margins,
                                  const int* eos_ids, int n_eos, int pad_id, int B, int V, int ldl, float rep_penalty,
                                  int step, int out_stride, float* scratch, hipStream_t stream) {
-    return sample_greedy_impl(logits, seen, cur_tok, finished, out_ids, margins, eos_ids, n_eos, pad_id, B, V, ldl, rep_penalty,
-                              step, out_stride, scratch, nullptr, nullptr, 0, stream);
+    return o3v_sample_greedy_ex(logits, seen, cur_tok, finished, out_ids, margins, eos_ids, n_eos, pad_id, B, V, ldl, rep_penalty,
+                                step, out_stride, scratch, nullptr, nullptr, 0, nullptr, stream);
 }
 
 // The same, and the chosen token's embedding row goes to x_out[b] (bf16 [B, hidden]) -- what the next decode forward
@@ -808,8 +810,8 @@ extern "C" int o3v_sample_greedy_embed(const void* logits, void* seen, int* cur_
                                        float rep_penalty, int step, int out_stride, float* scratch, const void* embed,
                                        void* x_out, int hidden, hipStream_t stream) {
     if (!embed) return O3V_ERR_ARG;
-    return sample_greedy_impl(logits, seen, cur_tok, finished, out_ids, margins, eos_ids, n_eos, pad_id, B, V, ldl, rep_penalty,
-                              step, out_stride, scratch, embed, x_out, hidden, stream);
+    return o3v_sample_greedy_ex(logits, seen, cur_tok, finished, out_ids, margins, eos_ids, n_eos, pad_id, B, V, ldl, rep_penalty,
+                                step, out_stride, scratch, embed, x_out, hidden, nullptr, stream);
 }
 
 // mark prompt ids as seen (repetition penalty covers prompt + generated, TF:logits_process.py:404-414)

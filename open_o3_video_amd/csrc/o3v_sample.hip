@@ -17,6 +17,7 @@
 //   pass E  kept mass {e >= tau} per thread, block scan, the thread holding the drawn target walks its own elements
 // RNG: counter-based (splitmix64 of seed, completion id, step) so a completion is reproducible wherever it is generated
 // (SURVEY.md section 8e).
+#include "../../include/o3v.h"
 #include "o3v_common.h"
 
 namespace {
@@ -365,7 +366,7 @@ __global__ __launch_bounds__(NT) void sample_draw_kernel(const bf16_t* __restric
                                                          float* __restrict__ chosen_lp, const int* __restrict__ eos_ids,
                                                          int n_eos, int pad_id, int V, int ldl, float rep, float temp,
                                                          uint64_t seed, const int* __restrict__ row_id, int step,
-                                                         int out_stride) {
+                                                         int out_stride, uint8_t* __restrict__ seen_prev) {
     __shared__ u64 red[NT / 64];
     const int blk = blockIdx.x, b = blockIdx.y;
     const u64* ws = wsp + (size_t)b * (WS_FLOATS / 2);
@@ -411,6 +412,7 @@ __global__ __launch_bounds__(NT) void sample_draw_kernel(const bf16_t* __restric
         if (!fin)
             for (int k = 0; k < n_eos; ++k)
                 if (tok == eos_ids[k]) finished[b] = 1;
+        if (seen_prev) seen_prev[b] = (tok >= 0 && tok < V) ? seen[(size_t)b * V + tok] : 0;  // log-probs see the map before this step
         if (tok >= 0 && tok < V) seen[(size_t)b * V + tok] = 1;
         cur_tok[b] = tok;
         out_ids[(size_t)b * out_stride + step] = tok;
@@ -418,12 +420,265 @@ __global__ __launch_bounds__(NT) void sample_draw_kernel(const bf16_t* __restric
     }
 }
 
+
+// ------------------------------------------------------------------------------------------------
+// Top-N log-probs (vLLM 0.7.2 SamplingParams.logprobs / prompt_logprobs, V0 sampler: log-probs of the PROCESSED distribution).
+// Run after the sampler of a decode step, on the scores it drew from: penalty from the seen map as it was BEFORE the step set the
+// chosen token (the sampler leaves that byte in seen_prev), then temperature; sampling rows keep only the tokens the draw kept
+// (top-k key >= kth, e >= tau, read from the sampler's row workspace) and renormalise over the kept mass -- the same 2^-40 integer
+// sum the draw walked, so log-probs and draw agree.  Greedy rows: penalty only, temperature 1, log-softmax over the whole row.
+//   LP1  grid (nblk, rows): per slice the N largest keys (score key << 32 | ~id: larger = higher score, then lower id; all keys
+//        distinct, so "ties to the lower id" is exact), the count of (kept) scores strictly above the chosen token's and, for greedy /
+//        prompt rows, the slice's max and sum exp(s - max)
+//   LP2  one wave per row: merges the nblk * N keys, the counts and the (max, sum) pairs
+// Selection (N <= 20, the row L2-resident after the lm_head): every wave keeps a sorted top-N list in lanes 0..N-1.  A batch of 64
+// candidates costs one compare + ballot against the list's N-th key; only the few that beat it are inserted (ballot popcount for
+// the slot, one shfl_up to shift).  For a 4.7k-element slice that is ~N ln(slice / N) ~ 100 insertions per block, all in registers:
+// no LDS histogram and no second radix select (which would cost three more passes over the row with their atomics).
+// ------------------------------------------------------------------------------------------------
+constexpr int LP_MAXN = 20;                              // O3V_MAX_LOGPROBS
+constexpr int LP_REC = 24;                               // u64 per slice record: LP_MAXN keys, greater-count, {max, sum}
+constexpr int LP_OFF = 18432;                            // u64 offset of a row's records inside its sampler scratch row
+constexpr int LP_SEEN_PREV = LP_OFF + NBLK * LP_REC;     // row 0 only: u8 [B <= 32] chosen tokens' seen bytes before the step
+constexpr int LP_NB_ROWS = 8;                            // slices per row of the prompt-side entry (many rows in flight)
+static_assert(WS_U64 <= LP_OFF && LP_SEEN_PREV + 4 <= WS_FLOATS / 2, "log-prob records inside the sampler scratch row");
+static_assert(LP_NB_ROWS * LP_REC * 2 == 384, "O3V_LOGPROB_ROW_SCRATCH_FLOATS");
+
+__device__ __forceinline__ u64 shfl_u64(u64 v, int src) {
+    const unsigned lo = __shfl((unsigned)v, src, 64), hi = __shfl((unsigned)(v >> 32), src, 64);
+    return ((u64)hi << 32) | lo;
+}
+__device__ __forceinline__ u64 lp_key(float s, int i) { return ((u64)score_key(s) << 32) | (u64)(~(unsigned)i); }
+__device__ __forceinline__ int key_id(u64 k) { return (int)~(unsigned)k; }
+__device__ __forceinline__ float key_score(u64 k) {
+    const unsigned h = (unsigned)(k >> 32);
+    return __uint_as_float((h & 0x80000000u) ? (h & 0x7fffffffu) : ~h);
+}
+__device__ __forceinline__ void lse_merge(float& m, float& z, float om, float oz) {
+    const float M = fmaxf(m, om);
+    if (M == -INFINITY) return;
+    z = (m == -INFINITY ? 0.f : z * expf(m - M)) + (om == -INFINITY ? 0.f : oz * expf(om - M));
+    m = M;
+}
+
+// descending top-n keys of a wave: lane i < n holds the i-th largest seen so far (0 = empty); every call is wave-uniform
+struct WaveTopN {
+    u64 mine = 0, thr = 0;  // thr: key of lane n-1 (0 until n keys are held)
+    int n;
+    __device__ explicit WaveTopN(int n_) : n(n_) {}
+    __device__ void insert(u64 c) {
+        const int lane = threadIdx.x & 63;
+        const int pos = __popcll(__ballot(lane < n && mine > c));
+        const u64 up = shfl_up_u64(mine, 1);
+        if (lane == pos)
+            mine = c;
+        else if (lane > pos && lane < n)
+            mine = up;
+        thr = shfl_u64(mine, n - 1);
+    }
+    __device__ void offer(u64 c) {  // each lane offers one key (0: none)
+        u64 hot = __ballot(c > thr);
+        while (hot) {
+            const int L = __ffsll((long long)hot) - 1;
+            insert(shfl_u64(c, L));
+            hot &= ~(1ull << L);
+            hot &= __ballot(c > thr);
+        }
+    }
+};
+
+// score of the chosen / target token under the state it was drawn in (seen_prev NULL: raw logits, the prompt side)
+__device__ __forceinline__ float lp_token_score(const bf16_t* lr, int tok, int V, const uint8_t* seen_prev, int b, float rep,
+                                                float temp) {
+    if (tok < 0 || tok >= V) return -INFINITY;
+    float x = bf2f(lr[tok]);
+    if (seen_prev && rep != 1.0f && seen_prev[b]) x = (x < 0.f) ? x * rep : x / rep;
+    return x / temp;
+}
+
+// the sampler's kept set: top-k key and top-p threshold of pass E (sampling rows)
+struct KeptTest {
+    float mx;
+    unsigned kth, prefix;
+    __device__ bool operator()(float s) const {
+        if (score_key(s) < kth) return false;
+        return prefix == 0 || __float_as_uint(expf(s - mx)) >= prefix;
+    }
+};
+
+template <bool SAMPLED>
+__global__ __launch_bounds__(NT) void lp_partial_kernel(const bf16_t* __restrict__ logits, const uint8_t* __restrict__ seen,
+                                                        const u64* __restrict__ wsp, u64* __restrict__ recp, int rec_stride, int nblk,
+                                                        const int* __restrict__ tok_arr, const uint8_t* __restrict__ seen_prev, int V,
+                                                        int ldl, float rep, float temp, int n) {
+    __shared__ u64 s_keys[NT / 64][LP_MAXN];
+    __shared__ float s_m[NT / 64], s_z[NT / 64];
+    __shared__ unsigned s_c[NT / 64];
+    const int blk = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    Row r;
+    r.lr = logits + (size_t)b * ldl;
+    r.sr = seen ? seen + (size_t)b * V : nullptr;
+    r.V = V;
+    r.vec = ((V & 7) == 0) && ((ldl & 7) == 0) && ((reinterpret_cast<uintptr_t>(logits) & 15) == 0) &&
+            ((reinterpret_cast<uintptr_t>(seen) & 7) == 0);
+    r.rep = rep;
+    r.temp = temp;
+    KeptTest kept_test{0.f, 0u, 0u};
+    if (SAMPLED) {
+        const u64* ws = wsp + (size_t)b * (WS_FLOATS / 2);
+        kept_test = KeptTest{row_max(ws), (unsigned)ws[WS_KTH], (unsigned)ws[WS_PREFIX]};
+    }
+    const int tok = tok_arr[b];
+    const float s_tok = lp_token_score(r.lr, tok, V, seen_prev, b, rep, temp);
+    WaveTopN top(n);
+    unsigned cnt = 0;
+    float m = -INFINITY, z = 0.f;
+    const int NG = (V + 7) / 8, per = (NG + nblk - 1) / nblk;
+    const int g0 = blk * per, g1 = (g0 + per < NG) ? g0 + per : NG;
+    for (int base = g0 + wave * 64; base < g1; base += NT) {  // trip count uniform per wave (ballots below)
+        const int g = base + lane;
+        float s[8];
+        if (g < g1) {
+            if (r.sr) {
+                load_group(r, g, s);  // the sampler's own arithmetic
+            } else if (r.vec) {
+                const u32x4 lv = *reinterpret_cast<const u32x4*>(r.lr + g * 8);
+#pragma unroll
+                for (int k = 0; k < 8; ++k) s[k] = bf2f((bf16_t)((lv[k >> 1] >> (16 * (k & 1))) & 0xffffu));
+            } else {
+#pragma unroll
+                for (int k = 0; k < 8; ++k) s[k] = (g * 8 + k < V) ? bf2f(r.lr[g * 8 + k]) : -INFINITY;
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const int i = g * 8 + k;
+            const bool valid = g < g1 && i < V;
+            const float sk = (i == tok) ? s_tok : s[k];  // the chosen token as it was drawn (its seen byte has changed since)
+            bool kept = valid;
+            if (SAMPLED) kept = kept && kept_test(sk);
+            cnt += (kept && sk > s_tok) ? 1u : 0u;
+            if (!SAMPLED && valid && sk > -INFINITY) {
+                if (sk > m) {
+                    z = z * expf(m - sk) + 1.f;
+                    m = sk;
+                } else {
+                    z += expf(sk - m);
+                }
+            }
+            if (n > 0) top.offer(kept ? lp_key(sk, i) : 0ull);
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        cnt += (unsigned)__shfl_xor((int)cnt, o, 64);
+        const float om = __shfl_xor(m, o, 64), oz = __shfl_xor(z, o, 64);
+        lse_merge(m, z, om, oz);
+    }
+    if (lane < n) s_keys[wave][lane] = top.mine;
+    if (lane == 0) {
+        s_c[wave] = cnt;
+        s_m[wave] = m;
+        s_z[wave] = z;
+    }
+    __syncthreads();
+    if (wave != 0) return;
+    for (int w = 1; w < NT / 64; ++w) top.offer(lane < n ? s_keys[w][lane] : 0ull);
+    u64* rec = recp + (size_t)b * rec_stride + (size_t)blk * LP_REC;
+    if (lane < n) rec[lane] = top.mine;
+    if (lane == 0) {
+        for (int w = 1; w < NT / 64; ++w) {
+            cnt += s_c[w];
+            lse_merge(m, z, s_m[w], s_z[w]);
+        }
+        rec[LP_MAXN] = cnt;
+        float* mz = reinterpret_cast<float*>(rec + LP_MAXN + 1);
+        mz[0] = m;
+        mz[1] = z;
+    }
+}
+
+template <bool SAMPLED>
+__global__ __launch_bounds__(64) void lp_final_kernel(const bf16_t* __restrict__ logits, const u64* __restrict__ wsp,
+                                                      const u64* __restrict__ recp, int rec_stride, int nblk,
+                                                      const int* __restrict__ tok_arr, const uint8_t* __restrict__ seen_prev, int V,
+                                                      int ldl, float rep, float temp, int n, float* __restrict__ chosen_lp,
+                                                      int* __restrict__ chosen_rank, int* __restrict__ top_ids,
+                                                      float* __restrict__ top_lp, int out_stride, int col) {
+    __shared__ int s_ids[LP_MAXN];
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const u64* rec0 = recp + (size_t)b * rec_stride;
+    WaveTopN top(n);
+    const int ncand = nblk * n;
+    for (int c0 = 0; c0 < ncand; c0 += 64) {
+        const int j = c0 + lane;
+        top.offer(j < ncand ? rec0[(j / n) * LP_REC + j % n] : 0ull);
+    }
+    unsigned cnt = 0;
+    float m = -INFINITY, z = 0.f;
+    if (lane < nblk) {
+        cnt = (unsigned)rec0[lane * LP_REC + LP_MAXN];
+        const float* mz = reinterpret_cast<const float*>(rec0 + lane * LP_REC + LP_MAXN + 1);
+        m = mz[0];
+        z = mz[1];
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        cnt += (unsigned)__shfl_xor((int)cnt, o, 64);
+        const float om = __shfl_xor(m, o, 64), oz = __shfl_xor(z, o, 64);
+        lse_merge(m, z, om, oz);
+    }
+    // log-prob of a score s: s - (max + log Z) for greedy / prompt rows; (s - max) - log(kept mass) for sampling rows
+    const float lse = m + logf(z);
+    KeptTest kept_test{0.f, 0u, 0u};
+    float lmass = 0.f;
+    if (SAMPLED) {
+        const u64* ws = wsp + (size_t)b * (WS_FLOATS / 2);
+        u64 tot = 0;
+        for (int i = 0; i < NBLK; ++i) tot += ws[WS_BM + i];
+        kept_test = KeptTest{row_max(ws), (unsigned)ws[WS_KTH], (unsigned)ws[WS_PREFIX]};
+        lmass = (float)(log((double)tot) - 40.0 * 0.69314718055994530942);  // log of the kept mass relative to exp(max)
+    }
+    auto logprob = [&](float s) { return SAMPLED ? (s - kept_test.mx) - lmass : s - lse; };
+    const size_t pos = (size_t)b * out_stride + col;
+    const int tok = tok_arr[b];
+    const float s_tok = lp_token_score(logits + (size_t)b * ldl, tok, V, seen_prev, b, rep, temp);
+    const bool tok_kept = tok >= 0 && tok < V && (!SAMPLED || kept_test(s_tok));
+    if (lane == 0) {
+        chosen_lp[pos] = tok_kept ? logprob(s_tok) : -INFINITY;
+        chosen_rank[pos] = 1 + (int)cnt;
+    }
+    if (n == 0) return;
+    const int n_valid = __popcll(__ballot(lane < n && top.mine != 0));
+    if (lane < n) s_ids[lane] = top.mine ? key_id(top.mine) : -1;
+    if (lane < n_valid) {
+        top_ids[pos * n + lane] = key_id(top.mine);
+        top_lp[pos * n + lane] = logprob(key_score(top.mine));
+    }
+    __syncthreads();
+    if (lane == 0 && n_valid < n) {  // fewer than n tokens survive the masks: the masked ones follow at -inf, lowest ids first
+        int slot = n_valid;
+        for (int id = 0; slot < n && id < V; ++id) {
+            bool taken = false;
+            for (int q = 0; q < n_valid; ++q) taken |= s_ids[q] == id;
+            if (taken) continue;
+            top_ids[pos * n + slot] = id;
+            top_lp[pos * n + slot] = -INFINITY;
+            ++slot;
+        }
+        for (; slot < n; ++slot) {  // vocabulary smaller than n
+            top_ids[pos * n + slot] = -1;
+            top_lp[pos * n + slot] = -INFINITY;
+        }
+    }
+}
+
 }  // namespace
 
-extern "C" int o3v_sample_top_k_top_p(const void* logits, void* seen, int* cur_tok, int* finished, int* out_ids,
-                                      float* chosen_logprob, const int* eos_ids, int n_eos, int pad_id, int B, int V, int ldl,
-                                      float rep_penalty, float temperature, int top_k, float top_p, uint64_t seed,
-                                      const int* row_id, int step, int out_stride, float* scratch, hipStream_t stream) {
+int o3v_sample_top_k_top_p_ex(const void* logits, void* seen, int* cur_tok, int* finished, int* out_ids, float* chosen_logprob,
+                               const int* eos_ids, int n_eos, int pad_id, int B, int V, int ldl, float rep_penalty, float temperature,
+                               int top_k, float top_p, uint64_t seed, const int* row_id, int step, int out_stride, float* scratch,
+                               uint8_t* seen_prev, hipStream_t stream) {
     if (!logits || !seen || !cur_tok || !finished || !out_ids || !scratch || B < 0 || V <= 0 || step < 0 ||
         step >= out_stride || !(temperature > 0.f) || !(top_p > 0.f) || top_k < 0 || (reinterpret_cast<uintptr_t>(scratch) & 7))
         return O3V_ERR_ARG;
@@ -446,9 +701,17 @@ extern "C" int o3v_sample_top_k_top_p(const void* logits, void* seen, int* cur_t
     }
     O3V_KLAUNCH(sample_mass_kernel, grid, block, 0, stream, lg, sn, ws, V, ldl, rep_penalty, temperature, top_p);
     O3V_KLAUNCH(sample_draw_kernel, grid, block, 0, stream, lg, sn, ws, cur_tok, finished, out_ids, chosen_logprob, eos_ids, n_eos,
-                pad_id, V, ldl, rep_penalty, temperature, seed, row_id, step, out_stride);
+                pad_id, V, ldl, rep_penalty, temperature, seed, row_id, step, out_stride, seen_prev);
     O3V_CHECK_LAUNCH();
     return O3V_OK;
+}
+
+extern "C" int o3v_sample_top_k_top_p(const void* logits, void* seen, int* cur_tok, int* finished, int* out_ids,
+                                      float* chosen_logprob, const int* eos_ids, int n_eos, int pad_id, int B, int V, int ldl,
+                                      float rep_penalty, float temperature, int top_k, float top_p, uint64_t seed,
+                                      const int* row_id, int step, int out_stride, float* scratch, hipStream_t stream) {
+    return o3v_sample_top_k_top_p_ex(logits, seen, cur_tok, finished, out_ids, chosen_logprob, eos_ids, n_eos, pad_id, B, V, ldl,
+                                     rep_penalty, temperature, top_k, top_p, seed, row_id, step, out_stride, scratch, nullptr, stream);
 }
 
 extern "C" int o3v_sample_top_p(const void* logits, void* seen, int* cur_tok, int* finished, int* out_ids,
@@ -457,4 +720,73 @@ extern "C" int o3v_sample_top_p(const void* logits, void* seen, int* cur_tok, in
                                 int out_stride, float* scratch, hipStream_t stream) {
     return o3v_sample_top_k_top_p(logits, seen, cur_tok, finished, out_ids, chosen_logprob, eos_ids, n_eos, pad_id, B, V, ldl,
                                   rep_penalty, temperature, 0, top_p, seed, row_id, step, out_stride, scratch, stream);
+}
+
+// One decode step's sampler exactly as o3v_llm_decode runs it (greedy: penalty + argmax, the embedding row gathered when `embed` is
+// given; sampling: the top-k / top-p passes), then the two log-prob launches.  scratch: f32 [B, O3V_SAMPLE_SCRATCH_FLOATS] in both
+// modes (the log-prob records sit above what either sampler uses).
+int o3v_sample_lp_step(const void* logits, void* seen, int* cur_tok, int* finished, int* out_ids, float* margins, const int* eos_ids,
+                       int n_eos, int pad_id, int B, int V, int ldl, int do_sample, float rep_penalty, float temperature, int top_k,
+                       float top_p, uint64_t seed, const int* row_id, int step, int out_stride, float* scratch, const void* embed,
+                       void* x_out, int hidden, const o3v_logprob_opts* lp, hipStream_t stream) {
+    if (!lp || lp->n < 0 || lp->n > LP_MAXN || !lp->chosen_lp || !lp->chosen_rank || (lp->n > 0 && (!lp->top_ids || !lp->top_lp)) ||
+        !scratch || (reinterpret_cast<uintptr_t>(scratch) & 7) || B > 32 || ldl < V)
+        return O3V_ERR_ARG;
+    u64* ws = (u64*)scratch;
+    uint8_t* seen_prev = reinterpret_cast<uint8_t*>(ws + LP_SEEN_PREV);
+    if (do_sample) {
+        const int rc = o3v_sample_top_k_top_p_ex(logits, seen, cur_tok, finished, out_ids, margins, eos_ids, n_eos, pad_id, B, V, ldl,
+                                                 rep_penalty, temperature, top_k, top_p, seed, row_id, step, out_stride, scratch,
+                                                 seen_prev, stream);
+        if (rc != O3V_OK) return rc;
+    } else {
+        const int rc = o3v_sample_greedy_ex(logits, seen, cur_tok, finished, out_ids, margins, eos_ids, n_eos, pad_id, B, V, ldl,
+                                            rep_penalty, step, out_stride, scratch, embed, x_out, hidden, seen_prev, stream);
+        if (rc != O3V_OK) return rc;
+        temperature = 1.0f;  // the greedy sampler applies the penalty only
+    }
+    if (B == 0) return O3V_OK;
+    const bf16_t* lg = (const bf16_t*)logits;
+    const uint8_t* sn = (const uint8_t*)seen;
+    const int rs = WS_FLOATS / 2;
+    u64* rec = ws + LP_OFF;
+    if (do_sample) {
+        O3V_KLAUNCH(lp_partial_kernel<true>, dim3(NBLK, B), dim3(NT), 0, stream, lg, sn, ws, rec, rs, NBLK, cur_tok, seen_prev, V, ldl,
+                    rep_penalty, temperature, lp->n);
+        O3V_KLAUNCH(lp_final_kernel<true>, dim3(B), dim3(64), 0, stream, lg, ws, rec, rs, NBLK, cur_tok, seen_prev, V, ldl, rep_penalty,
+                    temperature, lp->n, lp->chosen_lp, lp->chosen_rank, lp->top_ids, lp->top_lp, out_stride, step);
+    } else {
+        O3V_KLAUNCH(lp_partial_kernel<false>, dim3(NBLK, B), dim3(NT), 0, stream, lg, sn, ws, rec, rs, NBLK, cur_tok, seen_prev, V, ldl,
+                    rep_penalty, temperature, lp->n);
+        O3V_KLAUNCH(lp_final_kernel<false>, dim3(B), dim3(64), 0, stream, lg, ws, rec, rs, NBLK, cur_tok, seen_prev, V, ldl, rep_penalty,
+                    temperature, lp->n, lp->chosen_lp, lp->chosen_rank, lp->top_ids, lp->top_lp, out_stride, step);
+    }
+    O3V_CHECK_LAUNCH();
+    return O3V_OK;
+}
+
+extern "C" int o3v_sample_logprobs(const void* logits, void* seen, int* cur_tok, int* finished, int* out_ids, float* margins,
+                                   const int* eos_ids, int n_eos, int pad_id, int B, int V, int ldl, int do_sample, float rep_penalty,
+                                   float temperature, int top_k, float top_p, uint64_t seed, const int* row_id, int step,
+                                   int out_stride, float* scratch, const o3v_logprob_opts* lp, hipStream_t stream) {
+    return o3v_sample_lp_step(logits, seen, cur_tok, finished, out_ids, margins, eos_ids, n_eos, pad_id, B, V, ldl, do_sample,
+                              rep_penalty, temperature, top_k, top_p, seed, row_id, step, out_stride, scratch, nullptr, nullptr, 0, lp,
+                              stream);
+}
+
+extern "C" int o3v_logprobs_rows(const void* logits, const int* target, int R, int V, int ldl, int n, float* target_lp,
+                                 int* target_rank, int* top_ids, float* top_lp, float* scratch, hipStream_t stream) {
+    if (!logits || !target || !target_lp || !target_rank || R < 0 || R > 65535 || V <= 0 || ldl < V || n < 0 || n > LP_MAXN ||
+        (n > 0 && (!top_ids || !top_lp)) || !scratch || (reinterpret_cast<uintptr_t>(scratch) & 7))
+        return O3V_ERR_ARG;
+    if (R == 0) return O3V_OK;
+    const bf16_t* lg = (const bf16_t*)logits;
+    u64* rec = (u64*)scratch;
+    const int rs = LP_NB_ROWS * LP_REC;
+    O3V_KLAUNCH(lp_partial_kernel<false>, dim3(LP_NB_ROWS, R), dim3(NT), 0, stream, lg, nullptr, nullptr, rec, rs, LP_NB_ROWS, target,
+                nullptr, V, ldl, 1.0f, 1.0f, n);
+    O3V_KLAUNCH(lp_final_kernel<false>, dim3(R), dim3(64), 0, stream, lg, nullptr, rec, rs, LP_NB_ROWS, target, nullptr, V, ldl, 1.0f,
+                1.0f, n, target_lp, target_rank, top_ids, top_lp, 1, 0);
+    O3V_CHECK_LAUNCH();
+    return O3V_OK;
 }

@@ -36,11 +36,25 @@ def _stream():
 
 
 @dataclass
+class Logprobs:
+    """Top-N log-probs of a run of positions (vLLM SamplingParams.logprobs / prompt_logprobs; o3v_logprob_opts in include/o3v.h)."""
+    token: torch.Tensor                # f32 [B, T]: log-prob of the emitted (decode) / target (prompt) token
+    rank: torch.Tensor                 # i32 [B, T]: 1 + tokens with a strictly larger log-prob
+    top_ids: torch.Tensor              # i32 [B, T, N]: descending log-prob, ties to the lower id
+    top: torch.Tensor                  # f32 [B, T, N]
+
+
+@dataclass
 class GenerateOutput:
     sequences: torch.Tensor            # i64 [B, S+T]
     margins: Optional[torch.Tensor]    # f32 [B, T]: greedy top1-top2 margin / sampled token log-prob
     n_steps: int
     timings: dict
+    # generate(logprobs=N): the processed distribution each token was drawn from, [B, n_steps(, N)]
+    logprobs: Optional[Logprobs] = None
+    # generate(prompt_logprobs=N): [B0, S-1(, N)] per prompt, column j = prompt token j+1 given the tokens before it (left-padded
+    # rows: the columns before the row's first real token carry no meaning)
+    prompt_logprobs: Optional[Logprobs] = None
 
 
 class O3VEngine:
@@ -391,7 +405,7 @@ class O3VEngine:
                  top_k: int = 0, num_return_sequences: int = 1, seed: int = 0, row_ids: Optional[Sequence[int]] = None,
                  vis_embeds: Optional[torch.Tensor] = None, steps_per_sync: int = 16, return_margins: bool = True,
                  sync_timings: bool = False, prefix_key=None, pixel_values_videos=None, video_grid_thw=None, video_frames=None,
-                 second_per_grid_ts=None, _fused_ok: bool = True) -> GenerateOutput:
+                 second_per_grid_ts=None, logprobs: int = 0, prompt_logprobs: int = 0, _fused_ok: bool = True) -> GenerateOutput:
         """HF-semantics generate.  `num_return_sequences=G` shares ONE ViT pass and ONE prefill across the G
         completions of a prompt (the reference recomputes both G times, TF:1493-1579) and fans the KV cache out.
 
@@ -399,7 +413,13 @@ class O3VEngine:
         K/V of the prompt is kept under that key; a later call with the same key prefills only the tokens after
         the longest common token prefix (V-STAR asks 5 questions per video with the frame block first,
         R:eval/test/test_vstar_multi_images.py:205-206,511-544; self-consistency draws N samples of one prompt,
-        R:eval/tts.py:47-123).  Causal attention makes the prefix K/V independent of what follows it."""
+        R:eval/tts.py:47-123).  Causal attention makes the prefix K/V independent of what follows it.
+
+        `logprobs=N` (0..20): per emitted token its log-prob, rank and the N most likely tokens under the processed distribution it
+        was drawn from (GenerateOutput.logprobs; o3v_logprob_opts).  `prompt_logprobs=N`: the same for every prompt token after the
+        first on the raw logits, from the prefill's hidden rows in chunks (GenerateOutput.prompt_logprobs).  A call asking for prompt
+        log-probs does not reuse (or store) prefix K/V under `prefix_key`: reused rows have no hidden state to score.  With both 0
+        nothing changes: no extra buffer, the same decode calls."""
         cfg, tc = self.cfg, self.cfg.text
         ids = np.asarray(input_ids.cpu() if torch.is_tensor(input_ids) else input_ids, dtype=np.int64)
         if ids.ndim == 1:
@@ -419,6 +439,10 @@ class O3VEngine:
         T = int(max_new_tokens)
         if T <= 0:
             raise ValueError(f"`max_new_tokens` must be greater than 0, but is {T}.")   # GenerationConfig.validate's rule
+        n_lp, n_plp = int(logprobs or 0), int(prompt_logprobs or 0)
+        for what, v in (("logprobs", n_lp), ("prompt_logprobs", n_plp)):
+            if not 0 <= v <= _lib.MAX_LOGPROBS:
+                raise ValueError(f"`{what}` must be in 0..{_lib.MAX_LOGPROBS}, got {v}")
         tm = {}
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)] if sync_timings else None
 
@@ -442,7 +466,7 @@ class O3VEngine:
         kc, vc = self.alloc_cache(B, Tmax)
         kc0 = vc0 = None
         past = 0
-        use_prefix = prefix_key is not None and B0 == 1 and int(pad[0]) == 0
+        use_prefix = prefix_key is not None and B0 == 1 and int(pad[0]) == 0 and n_plp == 0
         if use_prefix:
             past = self._prefix_lookup(prefix_key, ids[0])
         x = self.embed(ids, vis, first=past, n_image_rows=n_img_rows)
@@ -473,6 +497,7 @@ class O3VEngine:
                                                     ("pvv", pixel_values_videos), ("vgrid", vgrid), ("vframes", video_frames)))
             self._last_prompt = {"key": key, "kc0": kc0, "vc0": vc0, "x_last": x.view(B0, S - past, -1)[0, -1:, :].clone(),
                                  "deltas": np.array(deltas, copy=True)}
+        plp = self._prompt_logprobs(x.view(B0, S, -1), ids, n_plp) if n_plp else None
         last = x.view(B0, S - past, -1)[:, -1, :]               # left padding: every row ends at S-1
         logits0 = self.head(last)                               # [B0, V]
         logits = logits0.repeat_interleave(G, dim=0).contiguous() if G > 1 else logits0
@@ -528,7 +553,15 @@ class O3VEngine:
                 nsplit = -nsplit
         part_o = torch.empty(n_rep_total * 64 * tc.head_dim, dtype=torch.float32, device=self.dev)
         part_ml = torch.empty(n_rep_total * 64 * 2, dtype=torch.float32, device=self.dev)
-        scratch = torch.empty((B, _lib.SAMPLE_SCRATCH_FLOATS if do_sample else 256), dtype=torch.float32, device=self.dev)
+        scratch = torch.empty((B, _lib.SAMPLE_SCRATCH_FLOATS if do_sample or n_lp else 256), dtype=torch.float32, device=self.dev)
+        lp = lp_opts = None
+        if n_lp:
+            lp = Logprobs(token=torch.zeros((B, T), dtype=torch.float32, device=self.dev),
+                          rank=torch.zeros((B, T), dtype=torch.int32, device=self.dev),
+                          top_ids=torch.zeros((B, T, n_lp), dtype=torch.int32, device=self.dev),
+                          top=torch.zeros((B, T, n_lp), dtype=torch.float32, device=self.dev))
+            lp_opts = _lib.LogprobOpts(n=n_lp, chosen_lp=lp.token.data_ptr(), chosen_rank=lp.rank.data_ptr(),
+                                       top_ids=lp.top_ids.data_ptr(), top_lp=lp.top.data_ptr())
         xdec = torch.empty((B, H), dtype=torch.bfloat16, device=self.dev)
         nbytes = _lib.load().o3v_llm_workspace_bytes(C.byref(self.w.llm), B)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
@@ -571,7 +604,10 @@ class O3VEngine:
         while done < T:
             # the first chunk is short whenever the one-launch block is in use: its time-out word is read right after it
             n = min(chunk if (done or sync is None) else min(chunk, getattr(self, "_first_chunk", 16)), T - done)
-            _lib.call("o3v_llm_decode", C.byref(self.w.llm), C.byref(st), done, n, int(done + n == T), _stream())
+            if lp_opts is None:
+                _lib.call("o3v_llm_decode", C.byref(self.w.llm), C.byref(st), done, n, int(done + n == T), _stream())
+            else:
+                _lib.call("o3v_llm_decode_lp", C.byref(self.w.llm), C.byref(st), C.byref(lp_opts), done, n, int(done + n == T), _stream())
             first = done == 0
             done += n
             if first and done < T:
@@ -599,8 +635,33 @@ class O3VEngine:
             torch.cuda.synchronize()
             tm.update({"vit_ms": ev[0].elapsed_time(ev[1]), "prefill_ms": ev[1].elapsed_time(ev[2]),
                        "decode_ms": ev[2].elapsed_time(ev[3])})
+        if lp is not None:
+            lp = Logprobs(lp.token[:, :done], lp.rank[:, :done], lp.top_ids[:, :done], lp.top[:, :done])
         return GenerateOutput(sequences=seqs, margins=None if margins is None else margins[:, :done], n_steps=done,
-                              timings=tm)
+                              timings=tm, logprobs=lp, prompt_logprobs=plp)
+
+    def _prompt_logprobs(self, xs: torch.Tensor, ids: np.ndarray, n: int, rows_per_chunk: int = 2048) -> Logprobs:
+        """Prompt log-probs from the prefill's hidden rows xs [B0, S, H]: row j of prompt b predicts ids[b, j+1].  The head runs on
+        `rows_per_chunk` rows at a time (as completion_logps does); no [S, vocab] tensor is ever held."""
+        B0, S, H = xs.shape
+        V = self.cfg.text.vocab_size
+        out = Logprobs(token=torch.zeros((B0, S - 1), dtype=torch.float32, device=self.dev),
+                       rank=torch.zeros((B0, S - 1), dtype=torch.int32, device=self.dev),
+                       top_ids=torch.zeros((B0, S - 1, n), dtype=torch.int32, device=self.dev),
+                       top=torch.zeros((B0, S - 1, n), dtype=torch.float32, device=self.dev))
+        if S < 2:
+            return out
+        tgt = torch.from_numpy(np.ascontiguousarray(ids[:, 1:].astype(np.int32))).to(self.dev)
+        step = max(16, int(rows_per_chunk))
+        scratch = torch.empty((min(step, S - 1), _lib.LOGPROB_ROW_SCRATCH_FLOATS), dtype=torch.float32, device=self.dev)
+        for b in range(B0):
+            for r0 in range(0, S - 1, step):
+                r1 = min(S - 1, r0 + step)
+                lg = self.head(xs[b, r0:r1])
+                _lib.call("o3v_logprobs_rows", _ptr(lg), _ptr(tgt[b, r0:r1]), r1 - r0, V, V, n, _ptr(out.token[b, r0:r1]),
+                          _ptr(out.rank[b, r0:r1]), _ptr(out.top_ids[b, r0:r1]), _ptr(out.top[b, r0:r1]), _ptr(scratch), _stream())
+                del lg
+        return out
 
     # ------------------------------------------------------------------------------------------ prefix K/V
     PREFIX_ENTRIES = 2   # videos whose prompt K/V stay resident (7B, S=4.5k: 0.26 GB each; 288 GB HBM is not the limit)

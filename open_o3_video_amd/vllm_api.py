@@ -13,6 +13,8 @@ The engine tokenises `prompt` itself, expands each <|image_pad|> to gh*gw/4 plac
 process_vision_info under a <|vision_start|><|video_pad|><|vision_end|> prompt) is the native video input: temporal patches of two
 frames, one <|video_pad|> expanded to T/2*gh*gw/4 placeholders, rope time advancing per temporal patch.
 temperature == 0 -> greedy; otherwise temperature / top-p sampling with repetition penalty over prompt + output.
+`SamplingParams(logprobs=N, prompt_logprobs=N)` return vLLM's per-token {token_id: Logprob} dicts (V0 sampler semantics: the
+processed distribution each token was drawn from).
 """
 from __future__ import annotations
 
@@ -28,6 +30,8 @@ from .config import O3VConfig
 from .engine import O3VEngine
 from .weights import DeviceWeights, getter_from_safetensors_dir
 
+MAX_LOGPROBS = 20   # vLLM's default max_logprobs (the kernels' O3V_MAX_LOGPROBS)
+
 
 @dataclass
 class SamplingParams:
@@ -38,6 +42,21 @@ class SamplingParams:
     stop_token_ids: Optional[Sequence[int]] = None
     n: int = 1
     seed: Optional[int] = None
+    logprobs: Optional[int] = None          # per output token: its log-prob + the N most likely (0: the token's only)
+    prompt_logprobs: Optional[int] = None   # the same for every prompt token after the first
+
+    def __post_init__(self):
+        for name in ("logprobs", "prompt_logprobs"):
+            v = getattr(self, name)
+            if v is not None and not 0 <= int(v) <= MAX_LOGPROBS:
+                raise ValueError(f"Requested {name} of {v}, which is outside the allowed range 0..{MAX_LOGPROBS}")
+
+
+@dataclass
+class Logprob:
+    logprob: float
+    rank: Optional[int] = None
+    decoded_token: Optional[str] = None
 
 
 @dataclass
@@ -46,6 +65,8 @@ class CompletionOutput:
     text: str
     token_ids: List[int]
     finish_reason: str = "length"
+    cumulative_logprob: Optional[float] = None
+    logprobs: Optional[List[dict]] = None    # one {token_id: Logprob} per token of token_ids
 
 
 @dataclass
@@ -54,6 +75,28 @@ class RequestOutput:
     prompt: str
     prompt_token_ids: List[int]
     outputs: List[CompletionOutput] = field(default_factory=list)
+    prompt_logprobs: Optional[List[Optional[dict]]] = None   # None, then one {token_id: Logprob} per prompt token after the first
+
+
+def logprob_dicts(token_ids, token_lp, rank, top_ids, top_lp, n: int, decode=None) -> List[dict]:
+    """vLLM V0's per-position dict (sampler.py _get_sampled_logprob_if_needed / _get_prompt_logprob_if_needed): the position's own
+    token with its rank, then the n most likely tokens with ranks 1..n (which win when the token is among them).  Host arrays:
+    token_lp / rank [T], top_ids / top_lp [T, >= n]."""
+    dec = decode or (lambda t: None)
+    out = []
+    for j, t in enumerate(token_ids):
+        d = {int(t): Logprob(float(token_lp[j]), int(rank[j]), dec(int(t)))}
+        for k in range(n):
+            tid = int(top_ids[j][k])
+            if tid >= 0:
+                d[tid] = Logprob(float(top_lp[j][k]), k + 1, dec(tid))
+        out.append(d)
+    return out
+
+
+def _host_logprobs(lp):
+    """engine.Logprobs (device tensors) -> host arrays (token, rank, top_ids, top)."""
+    return None if lp is None else tuple(t.cpu().numpy() for t in (lp.token, lp.rank, lp.top_ids, lp.top))
 
 
 def _load_tokenizer(path):
@@ -282,6 +325,17 @@ class LLM:
         common = dict(max_new_tokens=sp.max_tokens, eos_token_ids=eos, pad_token_id=self.cfg.pad_token_id,
                       repetition_penalty=sp.repetition_penalty, do_sample=not greedy,
                       temperature=1.0 if greedy else sp.temperature, top_p=1.0 if greedy else sp.top_p, return_margins=False)
+        # logprobs=0 still reports the token's own log-prob: the engine is asked for at least one top entry (0 there means off)
+        n_lp = None if sp.logprobs is None else int(sp.logprobs)
+        n_plp = None if sp.prompt_logprobs is None else int(sp.prompt_logprobs)
+        if n_lp is not None:
+            common["logprobs"] = max(1, n_lp)
+        decode_memo = {}
+
+        def decode_one(t):
+            if t not in decode_memo:
+                decode_memo[t] = self.tokenizer.decode([t]) if hasattr(self.tokenizer, "decode") else None
+            return decode_memo[t]
         # ---- per request: frames -> (cached) visual tokens, prompt -> ids
         prepared = []
         tps = self.cfg.vision.temporal_patch_size
@@ -321,14 +375,24 @@ class LLM:
                 return None
             return parts[0] if len(parts) == 1 else torch.cat(parts, dim=-2)
 
-        def finish(ro, index, row, n_prompt):
+        def finish(ro, index, row, n_prompt, lp=None, i=0):
             toks = row[n_prompt:].tolist()
             reason = "length"
             for j, t in enumerate(toks):
                 if t in eos:
                     toks, reason = toks[:j], "stop"   # vLLM drops the stop token from the text
                     break
-            ro.outputs.append(CompletionOutput(index, self.tokenizer.decode(toks, skip_special_tokens=True), toks, reason))
+            co = CompletionOutput(index, self.tokenizer.decode(toks, skip_special_tokens=True), toks, reason)
+            if lp is not None:      # trimmed exactly as token_ids
+                tok_lp, rank, top_ids, top_lp = (a[i] for a in lp)
+                co.logprobs = logprob_dicts(toks, tok_lp, rank, top_ids, top_lp, n_lp, decode_one)
+                co.cumulative_logprob = float(np.sum(tok_lp[:len(toks)], dtype=np.float64))
+            ro.outputs.append(co)
+
+        def prompt_dicts(plp, i, ids, first_col):
+            """[None] + one dict per prompt token after the first; prompt token k is column first_col + k - 1 of row i."""
+            tok_lp, rank, top_ids, top_lp = (a[i, first_col:first_col + len(ids) - 1] for a in plp)
+            return [None] + logprob_dicts(ids[1:], tok_lp, rank, top_ids, top_lp, n_plp, decode_one)
 
         results = []
         if len(prepared) > 1 and sp.n == 1 and self.max_num_seqs > 1:
@@ -349,10 +413,14 @@ class LLM:
                                            video_grid_thw=np.concatenate(vgrid_parts) if vgrid_parts else None,
                                            second_per_grid_ts=spg_all or None,
                                            row_ids=[self._req + i for i in range(len(chunk))],
-                                           seed=0 if sp.seed is None else sp.seed, **common)
+                                           seed=0 if sp.seed is None else sp.seed,
+                                           prompt_logprobs=0 if n_plp is None else max(1, n_plp), **common)
+                lp, plp = _host_logprobs(out.logprobs), _host_logprobs(out.prompt_logprobs)
                 for i, p in enumerate(chunk):
                     ro = RequestOutput(request_id=str(self._req), prompt=p[0], prompt_token_ids=p[1])
-                    finish(ro, 0, out.sequences[i], L)
+                    finish(ro, 0, out.sequences[i], L, lp, i)
+                    if plp is not None:     # left padding: the row's first real token sits at column L - len(ids)
+                        ro.prompt_logprobs = prompt_dicts(plp, i, p[1], L - len(p[1]))
                     results.append(ro)
                     self._req += 1
             return results
@@ -366,10 +434,14 @@ class LLM:
                 out = self.engine.generate([ids], None, vis_embeds=vis, image_grid_thw=grid, video_grid_thw=vgrid,
                                            second_per_grid_ts=spg, num_return_sequences=g,
                                            row_ids=list(range(i0, i0 + g)), seed=self._req if sp.seed is None else sp.seed,
-                                           prefix_key=vkey if self.enable_prefix_caching else None, **common)
+                                           prefix_key=vkey if self.enable_prefix_caching else None,
+                                           prompt_logprobs=0 if n_plp is None or i0 else max(1, n_plp), **common)
                 self.prefix_tokens_reused += int(out.timings.get("prefix_tokens_reused", 0))
+                lp = _host_logprobs(out.logprobs)
+                if out.prompt_logprobs is not None:
+                    ro.prompt_logprobs = prompt_dicts(_host_logprobs(out.prompt_logprobs), 0, ids, 0)
                 for i in range(g):
-                    finish(ro, i0 + i, out.sequences[i], len(ids))
+                    finish(ro, i0 + i, out.sequences[i], len(ids), lp, i)
             results.append(ro)
             self._req += 1
         return results
