@@ -524,6 +524,30 @@ int o3v_llm_decode(const o3v_llm_desc* d, const o3v_decode_state* st, int step0,
 int o3v_llm_decode_lp(const o3v_llm_desc* d, const o3v_decode_state* st, const o3v_logprob_opts* lp, int step0, int n_steps,
                       int skip_last_forward, o3v_stream_t stream);
 
+/* ---- in-place weight update (vLLM / TRL model.load_weights after each optimizer step; R:grpo_trainer.py:581-586 generates
+ * from the weights being trained) ------------------------------------------------------------------------------------------ */
+#define O3V_SRC_BF16 0
+#define O3V_SRC_F32 1 /* rounded to nearest even as torch's .to(torch.bfloat16) does (every NaN -> 0x7FC0) */
+typedef struct {
+    const void* src;       /* [src_rows][src_ld] bf16 or f32 (src_dtype), one HF-named tensor */
+    const int* row_map;    /* optional, [nblk * 16]: source row of each destination row of the launched blocks, -1 = zero row;
+                              NULL: block i takes source rows 16 i .. 16 i + 15 */
+    const int* col_map;    /* optional, [cols]: source column of each destination column, -1 = zero column;
+                              NULL: columns 0 .. src_cols - 1, zeros after them */
+    void* dst;             /* bf16 [rows][cols] row-major image of the slot */
+    void* dst_frag;        /* optional bf16 fragment-major copy (rows % 16 == 0, cols % 32 == 0): [rows/16][cols/32][64][8] */
+    void* dst8;            /* optional fp8 e4m3fn codes [rows][cols], one power-of-two scale per row (o3v_quantize_rows_fp8's rule) */
+    float* dst8_scale;     /* [rows], needed with dst8 */
+    void* dst8_frag;       /* optional fp8 fragment-major copy (needs dst8; rows % 16 == 0, cols % 64 == 0): [rows/16][cols/64][64][16] */
+    int64_t src_ld;        /* elements; >= src_cols */
+    int src_dtype, src_rows, src_cols;   /* a source row >= src_rows is a zero row */
+    int rows, cols;        /* destination slot; cols % 16 == 0, every dst pointer 16-byte aligned */
+    int blk0, nblk, blk_stride;          /* destination row blocks blk0 + i * blk_stride (16 rows each), i < nblk */
+} o3v_repack_desc;
+/* Rewrites the destination row blocks of d in every image d names, from one read of the source (two with fp8 images: row amax,
+ * then the write pass).  Bytes equal a fresh DeviceWeights load of the same tensor; rows outside the blocks are not touched. */
+int o3v_repack_rows(const o3v_repack_desc* d, o3v_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -75,6 +75,14 @@ class PrefillOpts(C.Structure):
                 ("kprefix", vp), ("vprefix", vp), ("prefix_len", i32), ("prefix_cap", i32), ("rows_per_prefix", i32), ("w8a8", i32)]
 
 
+class RepackDesc(C.Structure):
+    _fields_ = [(n, vp) for n in ("src", "row_map", "col_map", "dst", "dst_frag", "dst8", "dst8_scale", "dst8_frag")] + \
+               [("src_ld", C.c_int64)] + [(n, i32) for n in ("src_dtype", "src_rows", "src_cols", "rows", "cols", "blk0", "nblk",
+                                                          "blk_stride")]
+
+
+SRC_BF16, SRC_F32 = 0, 1   # O3V_SRC_* in include/o3v.h
+
 # name -> argtypes (return type int unless listed in _RET)
 SIGNATURES = {
     "o3v_abi_version": [],
@@ -152,6 +160,7 @@ SIGNATURES = {
                             C.POINTER(LogprobOpts), vp],
     "o3v_logprobs_rows": [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp],
     "o3v_llm_decode_lp": [C.POINTER(LlmDesc), C.POINTER(DecodeState), C.POINTER(LogprobOpts), i32, i32, i32, vp],
+    "o3v_repack_rows": [C.POINTER(RepackDesc), vp],
 }
 _RET = {"o3v_ctx_create": vp, "o3v_ctx_destroy": None, "o3v_ctx_llm": C.POINTER(LlmDesc), "o3v_ctx_vit": C.POINTER(VitDesc),
         "o3v_ctx_vit3": C.POINTER(Vit3Desc), "o3v_vit_workspace_bytes": sz, "o3v_vit3_workspace_bytes": sz, "o3v_llm_workspace_bytes": sz, "o3v_decode_sync_bytes": sz}

@@ -16,6 +16,7 @@
 // applied in fp32 torch).
 #include "o3v_common.h"
 #include "o3v_gemm_tile.h"
+#include "o3v_fp8_rows.h"
 
 namespace {
 
@@ -299,22 +300,6 @@ __global__ __launch_bounds__(512) void gemm256ph_fp8_kernel(const uint8_t* __res
 // One wave per row; rows up to 16 chunks per lane (8192 columns) stay in registers, longer rows are read twice.
 // scale = 2^e, e = the smallest integer with amax / 2^e <= 448 (amax = 0: scale 1); q = fp8(y / scale) (exact division, RNE).
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float pow2_scale_for(float amax) {
-    if (!(amax > 0.f)) return 1.0f;
-    int e;
-    const float m = frexpf(amax, &e);  // amax = m * 2^e, m in [0.5, 1); 448 = 0.875 * 2^9: amax / 2^E <= 448 <=> m * 2^(e-E) <= 0.875 * 2^9
-    return ldexpf(1.0f, m <= 0.875f ? e - 9 : e - 8);
-}
-
-__device__ __forceinline__ uint2 pack8_fp8(const float (&y)[8], float inv) {
-    uint32_t lo = 0, hi = 0;
-    lo = __builtin_amdgcn_cvt_pk_fp8_f32(y[0] * inv, y[1] * inv, lo, false);
-    lo = __builtin_amdgcn_cvt_pk_fp8_f32(y[2] * inv, y[3] * inv, lo, true);
-    hi = __builtin_amdgcn_cvt_pk_fp8_f32(y[4] * inv, y[5] * inv, hi, false);
-    hi = __builtin_amdgcn_cvt_pk_fp8_f32(y[6] * inv, y[7] * inv, hi, true);
-    return make_uint2(lo, hi);
-}
-
 template <int MAXCH, bool NORM>
 __global__ __launch_bounds__(256) void rows_quant_fp8_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ w,
                                                              uint8_t* __restrict__ q, float* __restrict__ scale, int rows, int cols,

@@ -87,6 +87,9 @@ class O3VEngine:
         self.reuse_prompt_kv = os.environ.get("O3V_REUSE_PROMPT_KV", "1") != "0"
         self._last_prompt = None
         self.timings_last_logps = {}
+        # bumped by load_weights: every cache derived from the weights (prefix K/V, the hand-over, the Qwen3-VL position table
+        # in _vit_plan_cache, the vLLM facade's visual tokens) belongs to one version
+        self.weights_version = 0
         self.group_attention = os.environ.get("O3V_GROUP_ATTENTION", "1") != "0"   # A/B switch for the shared-prefix kernel
         self.fused_decode = os.environ.get("O3V_FUSED_DECODE", "1") != "0"         # A/B switch for the one-launch attention block
         self.group_attention_mode = os.environ.get("O3V_GROUP_MODE", "auto")
@@ -269,7 +272,8 @@ class O3VEngine:
         """Identity of a prompt for the generate -> log-prob hand-over: token ids, mask and rope positions as bytes, every visual input
         by shape, dtype and two 64-bit checksums of its bytes (a plain sum and a position-weighted one, computed where the tensor
         lives)."""
-        parts = [ids.tobytes(), mask.tobytes(), pos.tobytes(), self.position_mode]
+        # the weights version: a hand-over never crosses load_weights (getattr: the key is also computed for bare namespaces)
+        parts = [ids.tobytes(), mask.tobytes(), pos.tobytes(), self.position_mode, getattr(self, "weights_version", 0)]
         for name, t in tensors:
             if t is None:
                 parts.append((name, None))
@@ -685,6 +689,28 @@ class O3VEngine:
 
     def drop_prefix_cache(self):
         self._prefix = {}
+
+    def drop_prompt_handover(self):
+        """Release the generate -> completion_logps hand-over (the prompt's K/V and x_last).  It otherwise lives until the next
+        generate; load_weights drops it because it was computed with the old weights."""
+        self._last_prompt = None
+
+    # ------------------------------------------------------------------------------------------ weight update
+    def load_weights(self, named_tensors) -> set:
+        """New policy weights in place (vLLM's model.load_weights; the trainer calls it after each optimizer step): the packed
+        images are rewritten on the device by o3v_repack_rows (DeviceWeights.load_weights: same bytes as a fresh load, same data
+        pointers, enqueued on the current stream), then every cache derived from the weights is dropped.  Returns the canonical
+        names written."""
+        try:
+            return self.w.load_weights(named_tensors)
+        finally:
+            # also when a launch fails part-way: some slots may already hold the new bytes, so nothing derived from the old
+            # weights may be served again (the position table is dropped whether or not pos_embed was among the names)
+            self.weights_version += 1
+            self.drop_prefix_cache()
+            self.drop_prompt_handover()
+            if self.q3:
+                self._vit_plan_cache.clear()   # the resampled position table lives in the plan
 
     @staticmethod
     def _first_all_finished(gen: torch.Tensor, eos_ids, pad_id) -> int:

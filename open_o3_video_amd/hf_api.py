@@ -13,7 +13,7 @@ from __future__ import annotations
 
 import os
 from types import SimpleNamespace
-from typing import Optional
+from typing import List, NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -23,6 +23,11 @@ from .engine import O3VEngine
 from .weights import DeviceWeights, getter_from_dict, getter_from_safetensors_dir
 
 MAX_ROWS = 32  # sequences per engine call (O3VEngine.MAX_ROWS)
+
+
+class IncompatibleKeys(NamedTuple):
+    missing_keys: List[str]
+    unexpected_keys: List[str]
 
 
 class GenerationConfigLike(SimpleNamespace):
@@ -138,6 +143,29 @@ class Qwen2_5_VLForConditionalGeneration:
 
     def to(self, *_, **__):
         return self
+
+    # ---- new policy weights after an optimizer step (the trainer's model keeps training; this one generates)
+    def load_weights(self, weights) -> set:
+        """(name, tensor) pairs in any spelling the checkpoint loader accepts; see O3VEngine.load_weights."""
+        return self.engine.load_weights(weights)
+
+    def load_state_dict(self, state_dict, strict: bool = True):
+        """nn.Module.load_state_dict: strict requires every weight of the model and nothing else (RuntimeError otherwise);
+        strict=False writes what it knows and reports the rest.  Returns (missing_keys, unexpected_keys)."""
+        w = self.engine.w
+        known, unexpected, seen = [], [], set()
+        for k, t in state_dict.items():
+            try:
+                seen.add(w.resolve_name(k))
+                known.append((k, t))
+            except KeyError:
+                unexpected.append(k)
+        missing = sorted(set(w.update_plan) - seen)
+        if strict and (missing or unexpected):
+            raise RuntimeError(f"Error(s) in loading state_dict for {type(self).__name__}: missing keys {missing}, "
+                               f"unexpected keys {unexpected}")
+        self.load_weights(known)
+        return IncompatibleKeys(missing, unexpected)
 
     @property
     def device(self):

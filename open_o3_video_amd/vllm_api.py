@@ -20,6 +20,7 @@ from __future__ import annotations
 
 import os
 from dataclasses import dataclass, field
+from types import SimpleNamespace
 from typing import Any, List, Optional, Sequence
 
 import numpy as np
@@ -177,6 +178,28 @@ class LLM:
         # unpinned), "tf5" = transformers 5.15 (goldens G5b / G14 / G15); see indexing.rope_index
         self.position_mode = position_mode
 
+    # ---- new policy weights (GRPO / GSPO: the trainer pushes them after every optimizer step)
+    def load_weights(self, weights) -> set:
+        """vLLM's model.load_weights(iterable of (HF name, tensor)): packed weights rewritten in place on the GPU, then every
+        cache derived from them dropped (O3VEngine.load_weights)."""
+        done = self.engine.load_weights(weights)
+        self._vis_cache.clear()
+        return done
+
+    def reset_prefix_cache(self) -> bool:
+        self.engine.drop_prefix_cache()
+        self.engine.drop_prompt_handover()
+        return True
+
+    @property
+    def llm_engine(self):
+        """The attribute chain TRL pushes weights through after each step:
+        llm.llm_engine.model_executor.driver_worker.model_runner.model.load_weights(model.state_dict().items())."""
+        model = SimpleNamespace(load_weights=self.load_weights)
+        runner = SimpleNamespace(model=model)
+        return SimpleNamespace(model_executor=SimpleNamespace(driver_worker=SimpleNamespace(model_runner=runner)),
+                               reset_prefix_cache=self.reset_prefix_cache)
+
     # ---- multimodal input -> uint8/f32 frames [T,3,H,W] with H,W multiples of 28
     def _frames(self, mm) -> Optional[torch.Tensor]:
         if not mm:
@@ -252,7 +275,9 @@ class LLM:
         h = torch.zeros(2, dtype=torch.int64, device=fr.device)
         _lib.call("o3v_content_hash128", C.c_void_p(fr.data_ptr()), fr.numel() * fr.element_size(), C.c_void_p(h.data_ptr()),
                   C.c_void_p(torch.cuda.current_stream().cuda_stream))
-        key = ("video" if video else "image", tuple(fr.shape), str(fr.dtype)) + tuple(int(v) for v in h.tolist())
+        # the weights version keys the entry too: visual tokens computed before load_weights are never served after it
+        key = ("video" if video else "image", tuple(fr.shape), str(fr.dtype), self.engine.weights_version) + \
+            tuple(int(v) for v in h.tolist())
         hit = self._vis_cache.get(key)
         if hit is not None:
             self.vis_cache_hits += 1

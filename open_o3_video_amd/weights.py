@@ -85,6 +85,66 @@ def pad_cols(w: torch.Tensor, kpad: int) -> torch.Tensor:
     return out
 
 
+class _RepackWrite:
+    """One o3v_repack_rows launch: 16-row blocks row0 + i * stride (i < nblk) of slot `slot` and of its derived images."""
+
+    def __init__(self, slot, row0, nblk, stride, row_map=None, col_map=None, frag=None, q8=None, q8s=None, q8frag=None):
+        self.slot, self.row0, self.nblk, self.stride, self.row_map, self.col_map = slot, row0, nblk, stride, row_map, col_map
+        self.frag, self.q8, self.q8s, self.q8frag = frag, q8, q8s, q8frag
+
+    def apply(self, t: Dict[str, torch.Tensor], src: torch.Tensor, stream):
+        if src.stride(-1) != 1 or src.data_ptr() % 16:
+            src = src.contiguous()
+        dst = t[self.slot]
+
+        def ptr(key):
+            return t[key].data_ptr() if key else None
+
+        d = _lib.RepackDesc(src=src.data_ptr(), row_map=None if self.row_map is None else self.row_map.data_ptr(),
+                            col_map=None if self.col_map is None else self.col_map.data_ptr(), dst=dst.data_ptr(),
+                            dst_frag=ptr(self.frag), dst8=ptr(self.q8), dst8_scale=ptr(self.q8s), dst8_frag=ptr(self.q8frag),
+                            src_ld=src.stride(0), src_dtype=_lib.SRC_F32 if src.dtype == torch.float32 else _lib.SRC_BF16,
+                            src_rows=src.shape[0], src_cols=src.shape[1], rows=dst.shape[0], cols=dst.shape[1], blk0=self.row0,
+                            nblk=self.nblk, blk_stride=self.stride)
+        _lib.call("o3v_repack_rows", C.byref(d), C.c_void_p(stream.cuda_stream))
+
+    def bytes_written(self, t) -> int:
+        rows = min(16 * self.nblk, t[self.slot].shape[0] - 16 * self.row0) if self.stride == 1 else 16 * self.nblk
+        cols = t[self.slot].shape[1]
+        n = rows * cols * (2 * (1 + (self.frag is not None)) + (self.q8 is not None) + (self.q8frag is not None))
+        return n + (4 * rows if self.q8s else 0)
+
+
+class _VectorWrite:
+    """A norm / bias vector: slot[dst] = bf16(src) (src_idx: gather, -1 = zero), an in-place device copy."""
+
+    def __init__(self, slot, dst, src_idx=None):
+        self.slot, self.dst, self.src_idx = slot, dst, src_idx
+
+    def apply(self, t: Dict[str, torch.Tensor], src: torch.Tensor, stream):
+        v = src.to(torch.bfloat16)          # _Getter's conversion
+        if self.src_idx is None:
+            t[self.slot][self.dst].copy_(v)
+        else:
+            vals = torch.where(self.src_idx >= 0, v[self.src_idx.clamp(min=0)], torch.zeros((), dtype=v.dtype, device=v.device))
+            if isinstance(self.dst, slice):
+                t[self.slot][self.dst].copy_(vals)
+            else:
+                t[self.slot].index_copy_(0, self.dst, vals)
+
+    def bytes_written(self, t) -> int:
+        return 2 * (t[self.slot][self.dst].numel() if isinstance(self.dst, slice) else self.dst.numel())
+
+
+class UpdateEntry:
+    """What load_weights does with one HF name: its expected shape (alt_shapes: other accepted views, the Conv3d patch weight)
+    and the writes that put it where DeviceWeights packed it."""
+
+    def __init__(self, name, shape, writes):
+        self.name, self.shape, self.writes, self.alt_shapes = name, shape, writes, ()
+        self.unsupported = None   # why o3v_repack_rows cannot rewrite this weight's layout (load_weights raises)
+
+
 class _Getter:
     def __init__(self, fn: Callable[[str], torch.Tensor], device):
         self.fn, self.device = fn, device
@@ -189,6 +249,7 @@ class DeviceWeights:
                 keep["l.head8p"] = pack_mfma_fragments_fp8(keep["l.head8"])
                 self.llm.lm_head8p = keep["l.head8p"].data_ptr()
         self._check_shapes()
+        self._record_update_plan()
 
     def _pack_vision(self, v):
         """Qwen2.5-VL tower (TF:408-471)."""
@@ -301,6 +362,207 @@ class DeviceWeights:
             raise _lib.O3VError(f"unsupported head_dim (vision {vc.head_dim}, text {tc.head_dim})")
         if tc.num_attention_heads // tc.num_key_value_heads > 8:
             raise _lib.O3VError("GQA group size > 8 not supported by the decode attention kernel")
+
+    # ------------------------------------------------------------------------------------ in-place update (load_weights)
+    def _record_update_plan(self):
+        """One UpdateEntry per accepted HF name (canonical spelling: model.language_model.* / model.visual.* / lm_head.weight):
+        where the packing above put that tensor's values, restated as o3v_repack_rows launches (matrices) or in-place copies
+        (vectors).  Derived images are planned exactly where the packing made them (the keys present in self.t)."""
+        keep, vc, tc, dev = self.t, self.cfg.vision, self.cfg.text, self.device
+        plan: Dict[str, UpdateEntry] = {}
+        self.update_plan, self._update_alias = plan, {}
+
+        def images(slot):
+            return dict(frag=slot + "p" if slot + "p" in keep else None, q8=slot + "8" if slot + "8" in keep else None,
+                        q8s=slot + "8s" if slot + "8s" in keep else None, q8frag=slot + "8p" if slot + "8p" in keep else None)
+
+        def mat(name, shape, slot, row0=0, stride=1, nblk=None, row_map=None, col_map=None, derived=None, llm=False, why=None):
+            # a layout the kernel cannot rewrite is recorded as unsupported (load_weights refuses it); loading never fails here
+            rows, cols = keep[slot].shape
+            if nblk is None:
+                nblk = (rows - 16 * row0 + 15) // 16 if stride == 1 else rows // 16 // stride
+            if cols % 16:
+                why = why or f"{slot} is {cols} columns wide (o3v_repack_rows needs a multiple of 16)"
+            if llm and not (row0 * 16 + (nblk - 1) * 16 * stride + 16 <= rows and rows % 16 == 0):
+                # every 16-row block of an LLM slot comes from this one source: whole fragment KiB per k-step
+                why = why or f"{slot}: {rows} rows are not whole 16-row blocks of one source"
+            if row_map is not None and row_map.numel() < 16 * nblk:   # the kernel reads one entry per row of every launched block
+                row_map = torch.cat([row_map, row_map.new_full((16 * nblk - row_map.numel(),), -1)])
+            w = _RepackWrite(slot, row0, nblk, stride, row_map, col_map, **((derived or images(slot)) if llm else {}))
+            plan[name] = UpdateEntry(name, tuple(shape), [] if why else [w])
+            plan[name].unsupported = why
+            return plan[name]
+
+        def vec(name, n, slot, dst=None, src_idx=None):
+            plan[name] = UpdateEntry(name, (n,), [_VectorWrite(slot, slice(0, n) if dst is None else dst, src_idx)])
+
+        def gate_up_idx(n_src, ipad, half):   # pack_gate_up on vectors: destination positions of gate (half 0) / up (half 1)
+            g = torch.arange(ipad, device=dev)
+            dst = (g // 16) * 32 + half * 16 + g % 16
+            return dst, torch.where(g < n_src, g, torch.full_like(g, -1))
+
+        L, V = "model.language_model.", "model.visual."
+        H, D, nq, nkv, I = tc.hidden_size, tc.head_dim, tc.num_attention_heads, tc.num_key_value_heads, tc.intermediate_size
+        for i in range(tc.num_hidden_layers):
+            b, k = f"{L}layers.{i}.", f"l{i}."
+            vec(b + "input_layernorm.weight", H, k + "ln1")
+            vec(b + "post_attention_layernorm.weight", H, k + "ln2")
+            off = 0
+            for p, n in (("q", nq * D), ("k", nkv * D), ("v", nkv * D)):
+                mat(f"{b}self_attn.{p}_proj.weight", (n, H), k + "qkv_w", row0=off // 16, nblk=max(n // 16, 1), llm=True,
+                    why=None if off % 16 == 0 and n % 16 == 0 else "q / k / v rows are not whole 16-row blocks")
+                if tc.attention_bias:
+                    vec(f"{b}self_attn.{p}_proj.bias", n, k + "qkv_b", dst=slice(off, off + n))
+                off += n
+            if tc.qk_norm:
+                vec(b + "self_attn.q_norm.weight", D, k + "q_norm")
+                vec(b + "self_attn.k_norm.weight", D, k + "k_norm")
+            mat(b + "self_attn.o_proj.weight", (H, nq * D), k + "o_w", llm=True)
+            for half, p in enumerate(("gate", "up")):
+                mat(f"{b}mlp.{p}_proj.weight", (I, H), k + "gu_w", row0=half, stride=2, llm=True)
+            mat(b + "mlp.down_proj.weight", (H, I), k + "down_w", llm=True)
+        vec(L + "norm.weight", H, "l.norm")
+        head = dict(frag="l.headp" if "l.headp" in keep else None, q8="l.head8" if "l.head8" in keep else None,
+                    q8s="l.head8s" if "l.head8s" in keep else None, q8frag="l.head8p" if "l.head8p" in keep else None)
+        none = dict(frag=None, q8=None, q8s=None, q8frag=None)
+        if tc.tie_word_embeddings:   # l.head IS l.embed: the embedding refreshes the head's derived images too
+            mat(L + "embed_tokens.weight", (tc.vocab_size, H), "l.embed", derived=head, llm=True)
+            self._update_alias["lm_head.weight"] = L + "embed_tokens.weight"
+        else:
+            mat(L + "embed_tokens.weight", (tc.vocab_size, H), "l.embed", derived=none, llm=True)
+            mat("lm_head.weight", (tc.vocab_size, H), "l.head", derived=head, llm=True)
+
+        vh, vi = vc.hidden_size, vc.intermediate_size
+        pe = mat(V + "patch_embed.proj.weight", (vh, vc.patch_k), "v.patch_w")
+        pe.alt_shapes = ((vh, vc.in_channels, vc.temporal_patch_size, vc.patch_size, vc.patch_size),)   # the Conv3d weight
+        if self.cfg.arch == "qwen3_vl":
+            self._plan_vision_q3(mat, vec)
+        else:
+            for i in range(vc.depth):
+                b, k = f"{V}blocks.{i}.", f"v{i}."
+                vec(b + "norm1.weight", vh, k + "norm1")
+                vec(b + "norm2.weight", vh, k + "norm2")
+                mat(b + "attn.qkv.weight", (3 * vh, vh), k + "qkv_w")
+                vec(b + "attn.qkv.bias", 3 * vh, k + "qkv_b")
+                mat(b + "attn.proj.weight", (vh, vh), k + "proj_w")
+                vec(b + "attn.proj.bias", vh, k + "proj_b")
+                for half, p in enumerate(("gate", "up")):
+                    mat(f"{b}mlp.{p}_proj.weight", (vi, vh), k + "gu_w", row0=half, stride=2)
+                    vec(f"{b}mlp.{p}_proj.bias", vi, k + "gu_b", *gate_up_idx(vi, vc.inter_pad, half))
+                mat(b + "mlp.down_proj.weight", (vh, vi), k + "down_w")
+                vec(b + "mlp.down_proj.bias", vh, k + "down_b")
+            mh = vh * vc.merge_unit
+            vec(V + "merger.ln_q.weight", vh, "v.ln_q")
+            mat(V + "merger.mlp.0.weight", (mh, mh), "v.m0_w")
+            vec(V + "merger.mlp.0.bias", mh, "v.m0_b")
+            mat(V + "merger.mlp.2.weight", (vc.out_hidden_size, mh), "v.m2_w")
+            vec(V + "merger.mlp.2.bias", vc.out_hidden_size, "v.m2_b")
+
+    def _plan_vision_q3(self, mat, vec):
+        """_pack_vision_q3's layout: head_rows as a row map (qkv) or a column map (proj), fc1 zero rows / columns, merger
+        norms of DeepStack width."""
+        vc, dev, V = self.cfg.vision, self.device, "model.visual."
+        hid, heads, hd, Dp, ip = vc.hidden_size, vc.num_heads, vc.head_dim, vc.head_dim_pad, vc.inter_pad
+        half, halfp = hd // 2, Dp // 2
+        j = torch.arange(Dp)
+        inner = torch.where(j < halfp, j, j - halfp)
+        src = (torch.arange(heads)[:, None] * hd + torch.where(j < halfp, inner, inner + half)[None, :]).reshape(-1)
+        head_map = torch.where((inner < half)[None, :].expand(heads, Dp).reshape(-1), src, torch.full_like(src, -1))
+        qkv_map = torch.cat([torch.where(head_map >= 0, head_map + p * hid, head_map) for p in range(3)])
+        qkv_map_dev = qkv_map.to(torch.int32).to(dev)
+        col_map_dev = head_map.to(torch.int32).to(dev)
+        vec(V + "patch_embed.proj.bias", hid, "v.patch_b")
+        mat(V + "pos_embed.weight", (vc.num_position_embeddings, hid), "v.pos_embed")
+        for i in range(vc.depth):
+            b, k = f"{V}blocks.{i}.", f"v{i}."
+            for n in ("norm1", "norm2"):
+                vec(b + n + ".weight", hid, k + n + "_w")
+                vec(b + n + ".bias", hid, k + n + "_b")
+            mat(b + "attn.qkv.weight", (3 * hid, hid), k + "qkv_w", nblk=(qkv_map.numel() + 15) // 16, row_map=qkv_map_dev)
+            vec(b + "attn.qkv.bias", 3 * hid, k + "qkv_b", slice(0, qkv_map.numel()), qkv_map.to(dev))
+            mat(b + "attn.proj.weight", (hid, hid), k + "proj_w", col_map=col_map_dev)
+            vec(b + "attn.proj.bias", hid, k + "proj_b")
+            mat(b + "mlp.linear_fc1.weight", (vc.intermediate_size, hid), k + "fc1_w")
+            vec(b + "mlp.linear_fc1.bias", vc.intermediate_size, k + "fc1_b")
+            mat(b + "mlp.linear_fc2.weight", (hid, vc.intermediate_size), k + "fc2_w")
+            vec(b + "mlp.linear_fc2.bias", hid, k + "fc2_b")
+        mh = hid * vc.merge_unit
+        for prefix, key, post in [("merger.", "v.m", False)] + [(f"deepstack_merger_list.{n}.", f"v.ds{n}", True)
+                                                               for n in range(len(vc.deepstack_visual_indexes))]:
+            nw = mh if post else hid
+            vec(V + prefix + "norm.weight", nw, key + ".norm_w")
+            vec(V + prefix + "norm.bias", nw, key + ".norm_b")
+            mat(V + prefix + "linear_fc1.weight", (mh, mh), key + ".fc1_w")
+            vec(V + prefix + "linear_fc1.bias", mh, key + ".fc1_b")
+            mat(V + prefix + "linear_fc2.weight", (vc.out_hidden_size, mh), key + ".fc2_w")
+            vec(V + prefix + "linear_fc2.bias", vc.out_hidden_size, key + ".fc2_b")
+
+    def resolve_name(self, name: str) -> str:
+        """Canonical plan name of an HF name in any spelling _Getter accepts; KeyError if the engine has no such weight."""
+        if name in self.update_plan:
+            return name
+        if name in self._update_alias:
+            return self._update_alias[name]
+        for alias, canon in (("visual.", "model.visual."), ("language_model.model.", "model.language_model."),
+                             ("model.", "model.language_model.")):
+            if name.startswith(alias) and canon + name[len(alias):] in self.update_plan:
+                return canon + name[len(alias):]
+        raise KeyError(name)
+
+    def load_weights(self, named_tensors) -> set:
+        """Rewrite the packed images in place from (HF name, tensor) pairs -- vLLM's model.load_weights.  Every image a slot keeps
+        (bf16 rows, fragment-major, fp8 codes + scales, fp8 fragment-major) gets the bytes a fresh DeviceWeights load of the same
+        tensors builds; data pointers do not change; rows a tensor does not own are not touched.  All pairs are validated before
+        anything is written (unknown name: KeyError; wrong shape or a dtype other than bf16 / fp32: ValueError; a layout the
+        kernel cannot rewrite: O3VError).  Matrices go through o3v_repack_rows, vectors (norms, biases) through in-place device
+        copies, all enqueued on torch's current stream.
+        Sources on this GPU are used where they are and record_stream'ed on that stream, so freeing one right after the call
+        (e.g. leaving a ZeRO-3 GatheredParameters context) is safe: its memory is not reused before the queued work has read it.
+        Other sources are staged to this GPU one tensor at a time (transient memory: the largest tensor); a host source's copy
+        is a pageable one, so it blocks the host until that tensor has arrived.  Device sources need no host synchronisation.
+        Returns the canonical names written.  Derived state outside this object (engine caches) is the caller's:
+        O3VEngine.load_weights invalidates it."""
+        items = []
+        for name, t in named_tensors:
+            key = self.resolve_name(name)
+            e = self.update_plan[key]
+            if not torch.is_tensor(t) or not t.is_floating_point():
+                raise ValueError(f"{name}: need a floating-point tensor, got {getattr(t, 'dtype', type(t))}")
+            if t.dtype not in (torch.bfloat16, torch.float32):
+                raise ValueError(f"{name}: dtype {t.dtype} (bf16 or fp32 sources only)")
+            if tuple(t.shape) != e.shape and tuple(t.shape) not in e.alt_shapes:
+                raise ValueError(f"{name}: shape {tuple(t.shape)}, the engine expects {e.shape}")
+            if e.unsupported:
+                raise _lib.O3VError(f"{name}: no in-place update for this layout ({e.unsupported})")
+            items.append((key, e, t.detach()))
+        if self.device.type != "cuda":
+            raise _lib.O3VError("load_weights rewrites the device images: it needs weights on a ROCm GPU")
+        target = self.t["l.embed"].device            # the resolved device (self.device may be a bare "cuda")
+        stream = torch.cuda.current_stream(target)
+        done = set()
+        with torch.cuda.device(target):
+            for key, e, t in items:
+                if t.device != target:
+                    t = t.to(target)                  # staged on `stream`: one source tensor alive at a time
+                else:
+                    t.record_stream(stream)
+                for w in e.writes:
+                    w.apply(self.t, t.reshape(e.shape), stream)
+                done.add(key)
+        return done
+
+    def update_bytes(self, names=None):
+        """(bytes read, bytes written) of a bf16-source update of `names` (default: every plan entry)."""
+        rd = wr = 0
+        for name in (self.update_plan if names is None else names):
+            e = self.update_plan[name]
+            n = 1
+            for s in e.shape:
+                n *= s
+            rd += 2 * n
+            for w in e.writes:
+                wr += w.bytes_written(self.t)
+        return rd, wr
 
     def nbytes(self):
         seen, n = set(), 0
