@@ -21,6 +21,11 @@ per step (RCCL over xGMI when the backend is nccl) -- the collective is inside t
 
 `--dump-outputs DIR`: after the timed steps, rank 0 writes what the last timed step returned to its caller as DIR/<name>.npy
 (float64).  Prompt, frames and weights are all seeded, so two builds run with the same arguments can be compared file for file.
+
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, the dump if asked for, the result line.
+`--full` adds everything else after the timed steps (each part can be left out with its --no-* option): the per-stage
+breakdown, the rollout leg, the batched-videos row, the kernel roofline, the fp8 rows and the CPU baselines.  At N = 1 the
+one-rank RCCL group, which only the rollout leg's collective uses, is created under `--full` alone.
 """
 from __future__ import annotations
 
@@ -331,6 +336,9 @@ def main():
     ap.add_argument("--frames", type=int, default=32)
     ap.add_argument("--res", default="train", choices=["train", "eval"])
     ap.add_argument("--model", default="7b", choices=["7b", "3b"])
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the stage breakdown, rollout leg, batched videos, roofline, fp8 rows "
+                         "and CPU baselines (the --no-* options below leave parts of it out)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-batched", action="store_true", help="skip the extra 16-videos-per-step throughput measurement")
     ap.add_argument("--no-roofline", action="store_true")
@@ -381,7 +389,7 @@ def main():
         dist = dist_
         if dist.get_world_size() != args.gpus:
             raise SystemExit(f"world size {dist.get_world_size()} != --gpus {args.gpus}")
-    elif backend == "nccl" and os.environ.get("O3V_BENCH_SOLO_GROUP", "1") != "0":
+    elif args.full and backend == "nccl" and os.environ.get("O3V_BENCH_SOLO_GROUP", "1") != "0":
         # N = 1: a one-rank RCCL group, so that the rollout leg's all_gather / barriers run through the library the N = 8 run uses
         try:
             import torch.distributed as dist_
@@ -441,12 +449,14 @@ def main():
     if args.dump_outputs and rank == 0:
         dump_outputs(args.dump_outputs, out)
 
+    # everything below the headline runs under --full only
+    full = args.full
     # per-stage breakdown (one extra, untimed, synchronised step)
-    stages = step(0, timings=True).timings
+    stages = step(0, timings=True).timings if full else None
 
     # second measured leg: GSPO rollout with the metrics all_gather inside the timed region
     roll = None
-    if not args.no_rollout:
+    if full and not args.no_rollout:
         pv = torch.rand((args.frames * (Hres // 14) * (Wres // 14), 1176), generator=gen, device=dev) * 4 - 2   # processor-shaped pixel_values
         grid = np.asarray([[1, Hres // 14, Wres // 14]] * args.frames, dtype=np.int64)
         roll = rollout_leg(cfg, eng, ids, pv, grid, dist, dev, T=args.rollout_tokens)
@@ -461,7 +471,7 @@ def main():
     world_n = dist.get_world_size() if dist else 1
     solo = world_n == 1
     batched = None
-    if not args.no_batched and rank == 0 and solo:
+    if full and not args.no_batched and rank == 0 and solo:
         NB = O3VEngine.MAX_ROWS
         vids8 = torch.randint(0, 256, (NB * args.frames, 3, Hres, Wres), generator=gen, dtype=torch.uint8, device=dev)
 
@@ -477,15 +487,14 @@ def main():
         assert o8.sequences.shape == (NB, S + args.new_tokens)
         batched = {"videos_per_step": NB, "tokens_per_s_per_gpu": round(NB * args.new_tokens / tb, 1),
                    "videos_per_min_per_gpu": round(NB / tb * 60.0, 1), "ms_per_step": round(tb * 1e3, 1)}
-    roof = None if (args.no_roofline or rank != 0) else kernel_roofline(eng)   # a fraction of a second: kept at every N
-    fused_flag = eng.fused_decode
+    roof = None if (not full or args.no_roofline or rank != 0) else kernel_roofline(eng)   # a fraction of a second: kept at every N
     wbytes = sum(eng.w.t[f"l{l}.{k}"].numel() * 2 for l in range(cfg.text.num_hidden_layers) for k in ("qkv_w", "o_w", "gu_w", "down_w"))
     wbytes += eng.w.t["l.head"].numel() * 2
 
     # extra (not `value`, which stays bf16): the same decode on fp8 (OCP e4m3fn) weight rows with per-row scales -- BASELINE
     # config #5's weight format; half the weight bytes per step
     fp8 = None
-    if not args.no_fp8 and rank == 0 and solo:
+    if full and not args.no_fp8 and rank == 0 and solo:
         del eng
         torch.cuda.empty_cache()
         eng8 = O3VEngine(cfg, DeviceWeights(cfg, random_getter(cfg, 1234, dev), dev, batched_decode=True, fp8_decode=True))
@@ -532,9 +541,6 @@ def main():
         n_gpus = dist.get_world_size() if dist else 1
         total_tokens = n_gpus * args.steps * args.new_tokens
         ms_per_step = dt / args.steps * 1e3
-        tc = cfg.text
-        kv_bytes = 2 * tc.num_hidden_layers * tc.num_key_value_heads * tc.head_dim * 2 * (S + args.new_tokens / 2)
-        dec_ms = stages.get("decode_ms", 0.0) / max(1, args.new_tokens)
         par = f"dp{n_gpus} (replica per GPU, independent videos, no data-path collective in the headline leg)"
         if dist:
             par += f"; torch.distributed backend {backend}" + (" -- REHEARSAL: every rank on cuda:0" if one_device else " (RCCL)")
@@ -547,15 +553,20 @@ def main():
                                    f"(EOS suppressed, repetition_penalty 1.05), batch 1 per GPU, random-init bf16 weights",
                        "parallelism": par},
             "videos_per_min": round(n_gpus * args.steps / dt * 60.0, 2),
-            "stage_ms": {k: round(v, 2) for k, v in stages.items() if k.endswith("_ms") or k == "prefix_tokens_reused"},
-            "decode_tokens_per_sec_per_gpu": round(1e3 / dec_ms, 1) if dec_ms else None,
-            "decode_step_hbm": {"algorithmic_bytes": int(wbytes + kv_bytes), "ms": round(dec_ms, 4),
-                                "achieved_GBps": round((wbytes + kv_bytes) / (dec_ms * 1e-3) / 1e9, 1) if dec_ms else None,
-                                "frac_of_8TBps": round((wbytes + kv_bytes) / (dec_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if dec_ms else None,
-                                "launches_per_layer": stages.get("launches_per_layer"),
-                                "fused_attention_layers": stages.get("fused_attention_layers"),
-                                "standalone_attention_layers": stages.get("standalone_attention_layers")},
         }
+        if stages is not None:
+            tc = cfg.text
+            kv_bytes = 2 * tc.num_hidden_layers * tc.num_key_value_heads * tc.head_dim * 2 * (S + args.new_tokens / 2)
+            dec_ms = stages.get("decode_ms", 0.0) / max(1, args.new_tokens)
+            rec["stage_ms"] = {k: round(v, 2) for k, v in stages.items() if k.endswith("_ms") or k == "prefix_tokens_reused"}
+            rec["decode_tokens_per_sec_per_gpu"] = round(1e3 / dec_ms, 1) if dec_ms else None
+            rec["decode_step_hbm"] = {
+                "algorithmic_bytes": int(wbytes + kv_bytes), "ms": round(dec_ms, 4),
+                "achieved_GBps": round((wbytes + kv_bytes) / (dec_ms * 1e-3) / 1e9, 1) if dec_ms else None,
+                "frac_of_8TBps": round((wbytes + kv_bytes) / (dec_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if dec_ms else None,
+                "launches_per_layer": stages.get("launches_per_layer"),
+                "fused_attention_layers": stages.get("fused_attention_layers"),
+                "standalone_attention_layers": stages.get("standalone_attention_layers")}
         if roll:
             rec["rollout"] = roll
         if batched:
@@ -564,7 +575,7 @@ def main():
             rec["roofline"] = roof
         if fp8:
             rec["fp8_decode"] = fp8
-        if not args.no_cpu_baseline and n_gpus == 1:
+        if full and not args.no_cpu_baseline and n_gpus == 1:
             rec["cpu_baseline"] = cpu_baseline(cfg_dict, args.frames, Hres, Wres, S, args.new_tokens)
             rec["cpu_baseline"]["config1_full"] = cpu_baseline_config1()
         sys.stdout.flush()
