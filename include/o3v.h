@@ -180,7 +180,14 @@ int o3v_gemv_norm_qkv_rope_fp8(const void* X, const void* norm_w, float eps, con
 /* ---- attention ---------------------------------------------------------------------------------------------- */
 /* tiles: int32[n_tiles][8] = {q_row0, q_rows (<= rows_per_tile), k_row0, k_len, causal_off, k_lo, batch, 0};
  * rows_per_tile 64 (ragged ViT windows) or 128 (prefill).
- * ViT varlen attention (TF:248-287) and causal GQA prefill attention (TF:186-208, :602-689). */
+ * ViT varlen attention (TF:248-287) and causal GQA prefill attention (TF:186-208, :602-689).
+ * Rounding points (u = 2^-8, the bf16 unit roundoff; p_j the exact softmax weights, ref = sum_j p_j v_j): scores, running
+ * max and sums in fp32; P is rounded to bf16 before P.V, but the row sum l adds the UNROUNDED p, as the reference rounds the
+ * already-normalised probabilities.  So out = sum_j p_j (1 + d_j) v_j with |d_j| <= u: the error is
+ * sum_j p_j d_j (v_j - ref) + ref * sum_j p_j d_j, and with the bf16 output
+ *   |out - ref| <= u * sum_j p_j |v_j - ref| + 2u * |ref|.
+ * The decode kernels below add the ROUNDED p into l instead; the common factor cancels and the bound is
+ *   |out - ref| <= u * sum_j p_j |v_j - ref| + u * |ref|     (tests/test_gpu_attention_edges.py checks both). */
 int o3v_attn_tiles(const void* Q, const void* K, const void* V, void* O, const int* tiles, int n_tiles, int rows_per_tile,
                    int Hq, int n_rep, int D, long q_ts, long k_ts, long k_hs, long k_bs, long v_ts, long v_hs, long v_bs,
                    long o_ts, float scale, o3v_stream_t stream);

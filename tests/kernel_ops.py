@@ -18,6 +18,14 @@ def _s():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+def _buf(shape, dtype, device, poison):
+    """Output / split-partial buffer: uninitialised, or all NaN with poison=True (a slot the kernels fail to write then
+    reaches the result as NaN)."""
+    if poison:
+        return torch.full(shape if isinstance(shape, (tuple, torch.Size)) else (shape,), float("nan"), dtype=dtype, device=device)
+    return torch.empty(shape, dtype=dtype, device=device)
+
+
 def rmsnorm(x, w, eps):
     out = torch.empty_like(x)
     _lib.call("o3v_rmsnorm", _p(x), _p(w), _p(out), x.shape[0], x.shape[1], x.stride(0), out.stride(0), float(eps), _s())
@@ -55,49 +63,54 @@ def vit_rope_(qkv, cos, sin, H, D):
     return qkv
 
 
-def attn_tiles(q, k, v, tiles, Hq, n_rep, D, q_ts, k_ts, k_hs, k_bs, v_ts, v_hs, v_bs, out, o_ts, scale, rows_per_tile=64):
+def attn_tiles(q, k, v, tiles, Hq, n_rep, D, q_ts, k_ts, k_hs, k_bs, v_ts, v_hs, v_bs, out, o_ts, scale, rows_per_tile=64,
+               poison=False):
+    if poison:
+        out.fill_(float("nan"))
     _lib.call("o3v_attn_tiles", _p(q), _p(k), _p(v), _p(out), _p(tiles), tiles.shape[0], rows_per_tile, Hq, n_rep, D, q_ts, k_ts, k_hs,
               k_bs, v_ts, v_hs, v_bs, o_ts, float(scale), _s())
     return out
 
 
-def attn_decode(q, kc, vc, k_lo, ctx, nsplit, scale):
+def attn_decode(q, kc, vc, k_lo, ctx, nsplit, scale, poison=False):
     B, Hq, D = q.shape
     _, Hkv, Tmax, _ = kc.shape
-    out = torch.empty_like(q)
     ns = abs(nsplit)  # negative nsplit selects the scalar (non-MFMA) kernel
-    po = torch.empty(B * Hq * ns * D, dtype=torch.float32, device=q.device)
-    pm = torch.empty(B * Hq * ns * 2, dtype=torch.float32, device=q.device)
+    out = _buf(q.shape, q.dtype, q.device, poison)
+    po = _buf(B * Hq * ns * D, torch.float32, q.device, poison)
+    pm = _buf(B * Hq * ns * 2, torch.float32, q.device, poison)
     _lib.call("o3v_attn_decode", _p(q), _p(kc), _p(vc), _p(out), _p(po), _p(pm), _p(k_lo), B, Hq, Hkv, D, ctx, Tmax, nsplit,
               float(scale), _s())
     return out
 
 
-def attn_decode_group(q, kc, vc, k_lo, G, prefix_len, ctx, nsplit_prefix, scale):
+def attn_decode_group(q, kc, vc, k_lo, G, prefix_len, ctx, nsplit_prefix, scale, poison=False):
     B, Hq, D = q.shape
     _, Hkv, Tmax, _ = kc.shape
-    out = torch.empty_like(q)
-    po = torch.empty(B * Hq * 64 * D, dtype=torch.float32, device=q.device)
-    pm = torch.empty(B * Hq * 64 * 2, dtype=torch.float32, device=q.device)
+    out = _buf(q.shape, q.dtype, q.device, poison)
+    po = _buf(B * Hq * 64 * D, torch.float32, q.device, poison)
+    pm = _buf(B * Hq * 64 * 2, torch.float32, q.device, poison)
     _lib.call("o3v_attn_decode_group", _p(q), _p(kc), _p(vc), _p(out), _p(po), _p(pm), _p(k_lo), B, G, Hq, Hkv, D, prefix_len, ctx,
               Tmax, nsplit_prefix, float(scale), _s())
     return out
 
 
-def attn_decode_group_prefix(q, kc_own, vc_own, kpre, vpre, rows_per_prompt, k_lo, G, prefix_len, ctx, nsplit_prefix, scale):
+def attn_decode_group_prefix(q, kc_own, vc_own, kpre, vpre, rows_per_prompt, k_lo, G, prefix_len, ctx, nsplit_prefix, scale, poison=False):
     """kc_own / vc_own [B, Hkv, Tmax_own, D]: generated tokens only; kpre / vpre [B / rows_per_prompt, Hkv, cap, D]."""
     B, Hq, D = q.shape
     _, Hkv, Tmax, _ = kc_own.shape
-    out = torch.empty_like(q)
-    po = torch.empty(B * Hq * 64 * D, dtype=torch.float32, device=q.device)
-    pm = torch.empty(B * Hq * 64 * 2, dtype=torch.float32, device=q.device)
+    out = _buf(q.shape, q.dtype, q.device, poison)
+    po = _buf(B * Hq * 64 * D, torch.float32, q.device, poison)
+    pm = _buf(B * Hq * 64 * 2, torch.float32, q.device, poison)
     _lib.call("o3v_attn_decode_group_prefix", _p(q), _p(kc_own), _p(vc_own), _p(kpre), _p(vpre), kpre.shape[2], rows_per_prompt, _p(out),
               _p(po), _p(pm), _p(k_lo), B, G, Hq, Hkv, D, prefix_len, ctx, Tmax, nsplit_prefix, float(scale), _s())
     return out
 
 
 def attn_tiles_prefix(q, k, v, kpre, vpre, p_hs, p_bs, prefix_len, rows_per_prefix, tiles, Hq, n_rep, D, q_ts, k_ts, k_hs, k_bs, v_ts,
-                      v_hs, v_bs, out, o_ts, scale, rows_per_tile=64):
+                      v_hs, v_bs, out, o_ts, scale, rows_per_tile=64, poison=False):
+    if poison:
+        out.fill_(float("nan"))
     _lib.call("o3v_attn_tiles_prefix", _p(q), _p(k), _p(v), _p(kpre), _p(vpre), p_hs, p_bs, prefix_len, rows_per_prefix, _p(out),
               _p(tiles), tiles.shape[0], rows_per_tile, Hq, n_rep, D, q_ts, k_ts, k_hs, k_bs, v_ts, v_hs, v_bs, o_ts, float(scale), _s())
     return out
