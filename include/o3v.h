@@ -333,6 +333,33 @@ int o3v_sample_logprobs(const void* logits, void* seen, int* cur_tok, int* finis
                         const int* eos_ids, int n_eos, int pad_id, int B, int V, int ldl, int do_sample, float rep_penalty,
                         float temperature, int top_k, float top_p, uint64_t seed, const int* row_id, int step, int out_stride,
                         float* scratch, const o3v_logprob_opts* lp, o3v_stream_t stream);
+/* The rest of vLLM 0.7.2's SamplingParams that is decided on the GPU, inside the sampler passes above (V0 sampler,
+ * vllm/model_executor/layers/sampler.py; a restatement, parity unpinned).  Per row and step, fp32 from the bf16 logit:
+ *   1. x += bias[i]: ONE dense vector holding logit_bias, -inf for banned tokens and for everything outside allowed_token_ids (the
+ *      logits processors that run before the sampler); while step < min_tokens the vector is bias_early, which also holds -inf at
+ *      every stop id (_apply_min_tokens_penalty)
+ *   2. the repetition penalty as everywhere else (apply_penalties: seen = prompt or output)
+ *   3. x -= frequency * c + presence * [c > 0], c = out_counts[b][i]: how often row b has emitted token i before this step
+ *      (apply_penalties; here in fp32, vLLM in the model dtype)
+ *   4. greedy: arg-max.  Sampling: temperature, top-k, top-p as o3v_sample_top_k_top_p, then min_p (_apply_min_p: drop
+ *      probs < min_p * max prob, i.e. exp(s - max) < min_p; the maximum always stays) as one more lower bound of the kept-set test.
+ * The sampler's last stage adds 1 (saturating at 65535) to out_counts[b][tok] for the token an unfinished row emits.  Log-probs see
+ * steps 1-4 with seen and c as they were before the step.  A zeroed struct runs the plain sampler's arithmetic: same ids, bit for bit. */
+typedef struct {
+    float min_p;              /* [0, 1]; 0 = off */
+    float presence, frequency;/* [-2, 2]; either non-zero needs out_counts */
+    int min_tokens;           /* >= 0; > 0 needs bias_early */
+    const float* bias;        /* f32 [vocab] or NULL, 16-byte aligned */
+    const float* bias_early;  /* f32 [vocab]: `bias` with every stop id at -inf, used while step < min_tokens */
+    uint16_t* out_counts;     /* u16 [B, vocab] or NULL, 16-byte aligned, zeroed by the caller before step 0 */
+} o3v_sampling_opts;
+/* One decode step as o3v_llm_decode_ex runs it: o3v_sample_logprobs with the controls of `so` (required); lp may be NULL (no
+ * log-probs).  O3V_ERR_ARG before any launch for: NaN or out-of-range min_p / penalties, negative min_tokens, a penalty without
+ * out_counts, min_tokens > 0 without bias_early, a pointer of `so` that is not 16-byte aligned.  scratch as o3v_sample_logprobs. */
+int o3v_sample_step_ex(const void* logits, void* seen, int* cur_tok, int* finished, int* out_ids, float* margins,
+                       const int* eos_ids, int n_eos, int pad_id, int B, int V, int ldl, int do_sample, float rep_penalty,
+                       float temperature, int top_k, float top_p, uint64_t seed, const int* row_id, int step, int out_stride,
+                       float* scratch, const o3v_logprob_opts* lp, const o3v_sampling_opts* so, o3v_stream_t stream);
 /* Prompt side (vLLM prompt_logprobs; R:grpo_trainer.py:371-384 for the target log-prob): the same selection on raw logits (no
  * penalty, temperature 1, no masks) of R <= 65535 rows; row r predicts target[r].  Outputs [R] and [R, n]. */
 #define O3V_LOGPROB_ROW_SCRATCH_FLOATS 384 /* per row */
@@ -530,6 +557,14 @@ int o3v_llm_decode(const o3v_llm_desc* d, const o3v_decode_state* st, int step0,
  * st->sample_scratch must hold O3V_SAMPLE_SCRATCH_FLOATS per row in greedy mode as well; B <= 32. */
 int o3v_llm_decode_lp(const o3v_llm_desc* d, const o3v_decode_state* st, const o3v_logprob_opts* lp, int step0, int n_steps,
                       int skip_last_forward, o3v_stream_t stream);
+
+/* The same with the sampling controls of o3v_sampling_opts; vLLM Sampler.forward (_apply_min_tokens_penalty, apply_penalties,
+ * _apply_top_k_top_p, _apply_min_p): so == NULL is o3v_llm_decode_lp exactly (same launches, same ids).  Otherwise every step runs
+ * the extended sampler kernels (no added launch) with `bias_early` while step < min_tokens, st->sample_scratch holds
+ * O3V_SAMPLE_SCRATCH_FLOATS per row in greedy mode as well, and B <= 32.  lp may be NULL.  `so` is checked as o3v_sample_step_ex
+ * checks it, before anything else. */
+int o3v_llm_decode_ex(const o3v_llm_desc* d, const o3v_decode_state* st, const o3v_logprob_opts* lp, const o3v_sampling_opts* so,
+                      int step0, int n_steps, int skip_last_forward, o3v_stream_t stream);
 
 /* ---- in-place weight update (vLLM / TRL model.load_weights after each optimizer step; R:grpo_trainer.py:581-586 generates
  * from the weights being trained) ------------------------------------------------------------------------------------------ */

@@ -70,6 +70,12 @@ class LogprobOpts(C.Structure):
     _fields_ = [("n", i32), ("chosen_lp", vp), ("chosen_rank", vp), ("top_ids", vp), ("top_lp", vp)]
 
 
+class SamplingOpts(C.Structure):
+    """o3v_sampling_opts: min_p, presence / frequency penalty, min_tokens, the two static-edit vectors, the output counts."""
+    _fields_ = [("min_p", f32), ("presence", f32), ("frequency", f32), ("min_tokens", i32), ("bias", vp), ("bias_early", vp),
+                ("out_counts", vp)]
+
+
 class PrefillOpts(C.Structure):
     _fields_ = [("ds_rows", vp), ("ds_src", vp), ("n_ds", i32), ("ds_feat", vp), ("n_deep", i32), ("ds_stride", i64),
                 ("kprefix", vp), ("vprefix", vp), ("prefix_len", i32), ("prefix_cap", i32), ("rows_per_prefix", i32), ("w8a8", i32)]
@@ -161,6 +167,10 @@ SIGNATURES = {
     "o3v_logprobs_rows": [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp],
     "o3v_llm_decode_lp": [C.POINTER(LlmDesc), C.POINTER(DecodeState), C.POINTER(LogprobOpts), i32, i32, i32, vp],
     "o3v_repack_rows": [C.POINTER(RepackDesc), vp],
+    "o3v_sample_step_ex": [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, f32, i32, f32, u64, vp, i32, i32, vp,
+                           C.POINTER(LogprobOpts), C.POINTER(SamplingOpts), vp],
+    "o3v_llm_decode_ex": [C.POINTER(LlmDesc), C.POINTER(DecodeState), C.POINTER(LogprobOpts), C.POINTER(SamplingOpts), i32, i32, i32,
+                          vp],
 }
 _RET = {"o3v_ctx_create": vp, "o3v_ctx_destroy": None, "o3v_ctx_llm": C.POINTER(LlmDesc), "o3v_ctx_vit": C.POINTER(VitDesc),
         "o3v_ctx_vit3": C.POINTER(Vit3Desc), "o3v_vit_workspace_bytes": sz, "o3v_vit3_workspace_bytes": sz, "o3v_llm_workspace_bytes": sz, "o3v_decode_sync_bytes": sz}
@@ -168,6 +178,7 @@ _RET = {"o3v_ctx_create": vp, "o3v_ctx_destroy": None, "o3v_ctx_llm": C.POINTER(
 SYNC_TMO_BYTE = 2048            # O3V_SYNC_TMO_BYTE in include/o3v.h
 SAMPLE_SCRATCH_FLOATS = 40960   # O3V_SAMPLE_SCRATCH_FLOATS in include/o3v.h
 MAX_LOGPROBS = 20               # O3V_MAX_LOGPROBS
+MAX_COUNT = 65535               # the u16 output counts of o3v_sampling_opts saturate here
 LOGPROB_ROW_SCRATCH_FLOATS = 384  # O3V_LOGPROB_ROW_SCRATCH_FLOATS
 
 _lib = None

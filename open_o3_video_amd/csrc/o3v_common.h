@@ -161,14 +161,35 @@ inline thread_local long long o3v_tl_launches = 0;  // (C++17 inline variable: o
         if (e__ != hipSuccess) return O3V_ERR_LAUNCH;       \
     } while (0)
 
+// ---- extended sampling controls of one decode step (o3v_sampling_opts resolved by the host: `bias` is the early vector while
+// step < min_tokens), passed by value to the `_x` sampler kernels
+struct o3v_samp_x {
+    const float* bias;   // f32 [V] static edits (logit_bias, -inf bans, complement of the allowed set) or NULL; 16-byte aligned
+    uint16_t* counts;    // u16 [B, V] output-token counts or NULL; 16-byte aligned
+    uint16_t* cnt_prev;  // u16 [B]: the emitted token's count before this step counted it (the log-prob pass needs it)
+    float pres, freq;    // presence / frequency penalty
+    unsigned minp_bits;  // bit pattern of min_p (0: off)
+};
+// last sampler stage: count the token an unfinished row emits (saturating), leave its earlier count for the log-probs
+__device__ __forceinline__ void o3v_count_token(const o3v_samp_x& x, int b, int V, int tok, bool fin) {
+    uint16_t c = 0;
+    if (tok >= 0 && tok < V) {
+        uint16_t* p = x.counts + (size_t)b * V + tok;
+        c = *p;
+        if (!fin && c < 65535) *p = (uint16_t)(c + 1);
+    }
+    if (x.cnt_prev) x.cnt_prev[b] = c;
+}
+
 // ---- entry points shared between translation units (C++ linkage, not part of include/o3v.h)
 // samplers with an optional u8 [B] `seen_prev`: the chosen token's seen byte before the step sets it (the log-prob pass needs the
 // repetition-penalty state the token was drawn under)
 int o3v_sample_greedy_ex(const void* logits, void* seen, int* cur_tok, int* finished, int* out_ids, float* margins,
                          const int* eos_ids, int n_eos, int pad_id, int B, int V, int ldl, float rep_penalty, int step,
                          int out_stride, float* scratch, const void* embed, void* x_out, int hidden, uint8_t* seen_prev,
-                         hipStream_t stream);
+                         const o3v_samp_x* sx, hipStream_t stream);
 int o3v_sample_top_k_top_p_ex(const void* logits, void* seen, int* cur_tok, int* finished, int* out_ids, float* chosen_logprob,
                                const int* eos_ids, int n_eos, int pad_id, int B, int V, int ldl, float rep_penalty, float temperature,
                                int top_k, float top_p, uint64_t seed, const int* row_id, int step, int out_stride, float* scratch,
-                               uint8_t* seen_prev, hipStream_t stream);
+                               uint8_t* seen_prev, const o3v_samp_x* sx, hipStream_t stream);
+// sx (optional, both samplers): the extended controls; the `_x` kernels run the same stages on the extended row

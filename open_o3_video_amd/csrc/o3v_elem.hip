@@ -673,20 +673,26 @@ __device__ __forceinline__ void top2_merge(float& best, int& bi, float& second, 
     }
 }
 
-// stage 1: grid (NB, B) x 256 threads, each block reduces a contiguous slice of the vocabulary to (best, idx, second)
-__global__ __launch_bounds__(256) void sample_greedy_partial_kernel(const bf16_t* __restrict__ logits,
-                                                                    const uint8_t* __restrict__ seen,
-                                                                    float* __restrict__ part, int V, int ldl,
-                                                                    float rep_penalty) {
+// stage 1: grid (NB, B) x 256 threads, each block reduces a contiguous slice of the vocabulary to (best, idx, second).
+// EX (the `_x` entry): the static edits are added before the repetition penalty and the count penalties follow it
+// (o3v_sampling_opts; the same arithmetic as o3v_sample.hip's load_group)
+template <bool EX>
+__device__ __forceinline__ void sample_greedy_partial_body(const bf16_t* __restrict__ logits, const uint8_t* __restrict__ seen,
+                                                           float* __restrict__ part, int V, int ldl, float rep_penalty,
+                                                           const o3v_samp_x& sx) {
     const int b = blockIdx.y, nb = blockIdx.x;
     const bf16_t* lr = logits + (size_t)b * ldl;
     const uint8_t* sr = seen + (size_t)b * V;
+    const float* bias = EX ? sx.bias : nullptr;
+    const uint16_t* cr = (EX && sx.counts) ? sx.counts + (size_t)b * V : nullptr;
     const int per = (V + GREEDY_NB - 1) / GREEDY_NB;
     const int i0 = nb * per, i1 = (i0 + per < V) ? i0 + per : V;
     float best = -INFINITY, second = -INFINITY;
     int bi = 0x7fffffff;
-    auto visit = [&](int i, float s, unsigned seen_byte) {
+    auto visit = [&](int i, float s, unsigned seen_byte, float bias_i = 0.f, unsigned c = 0) {
+        if (EX && bias) s += bias_i;
         if (rep_penalty != 1.0f && seen_byte) s = (s < 0.f) ? s * rep_penalty : s / rep_penalty;
+        if (EX && c) s = s - (sx.freq * (float)c + sx.pres);
         if (s > best) {
             second = best;
             best = s;
@@ -703,10 +709,27 @@ __global__ __launch_bounds__(256) void sample_greedy_partial_kernel(const bf16_t
             const uint4 lv = *reinterpret_cast<const uint4*>(lr + g * 8);
             const uint2 sv = *reinterpret_cast<const uint2*>(sr + g * 8);
             const uint32_t lw[4] = {lv.x, lv.y, lv.z, lv.w};
+            if (EX) {  // 32 bytes of edits and 16 bytes of counts beside them (the entry points check the 16-byte alignment)
+                float bv[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+                uint4 cv = {0u, 0u, 0u, 0u};
+                if (bias) {
+                    const float4 b0 = *reinterpret_cast<const float4*>(bias + g * 8), b1 = *reinterpret_cast<const float4*>(bias + g * 8 + 4);
+                    bv[0] = b0.x, bv[1] = b0.y, bv[2] = b0.z, bv[3] = b0.w, bv[4] = b1.x, bv[5] = b1.y, bv[6] = b1.z, bv[7] = b1.w;
+                }
+                if (cr) cv = *reinterpret_cast<const uint4*>(cr + g * 8);
+                const uint32_t cw[4] = {cv.x, cv.y, cv.z, cv.w};
+#pragma unroll
+                for (int k = 0; k < 8; ++k)
+                    visit(g * 8 + k, (k & 1) ? bf_hi(lw[k >> 1]) : bf_lo(lw[k >> 1]), ((k < 4 ? sv.x : sv.y) >> (8 * (k & 3))) & 0xffu,
+                          bv[k], (cw[k >> 1] >> (16 * (k & 1))) & 0xffffu);
+                continue;
+            }
 #pragma unroll
             for (int k = 0; k < 8; ++k)   // ascending index inside the lane: the first maximum wins, like torch.argmax
                 visit(g * 8 + k, (k & 1) ? bf_hi(lw[k >> 1]) : bf_lo(lw[k >> 1]), ((k < 4 ? sv.x : sv.y) >> (8 * (k & 3))) & 0xffu);
         }
+    } else if (EX) {
+        for (int i = i0 + threadIdx.x; i < i1; i += 256) visit(i, bf2f(lr[i]), sr[i], bias ? bias[i] : 0.f, cr ? cr[i] : 0u);
     } else {
         for (int i = i0 + threadIdx.x; i < i1; i += 256) visit(i, bf2f(lr[i]), sr[i]);
     }
@@ -733,15 +756,28 @@ __global__ __launch_bounds__(256) void sample_greedy_partial_kernel(const bf16_t
         p[2] = second;
     }
 }
+__global__ __launch_bounds__(256) void sample_greedy_partial_kernel(const bf16_t* __restrict__ logits,
+                                                                    const uint8_t* __restrict__ seen,
+                                                                    float* __restrict__ part, int V, int ldl,
+                                                                    float rep_penalty) {
+    sample_greedy_partial_body<false>(logits, seen, part, V, ldl, rep_penalty, o3v_samp_x{});
+}
+__global__ __launch_bounds__(256) void sample_greedy_partial_kernel_x(const bf16_t* __restrict__ logits,
+                                                                      const uint8_t* __restrict__ seen,
+                                                                      float* __restrict__ part, int V, int ldl,
+                                                                      float rep_penalty, o3v_samp_x sx) {
+    sample_greedy_partial_body<true>(logits, seen, part, V, ldl, rep_penalty, sx);
+}
 
-// stage 2: one wave per sequence merges the NB partials and applies the token bookkeeping
-__global__ __launch_bounds__(64) void sample_greedy_final_kernel(const float* __restrict__ part, uint8_t* __restrict__ seen,
-                                                                 int* __restrict__ cur_tok, int* __restrict__ finished,
-                                                                 int* __restrict__ out_ids, float* __restrict__ margins,
-                                                                 const int* __restrict__ eos_ids, int n_eos, int pad_id,
-                                                                 int V, int step, int out_stride,
-                                                                 const uint4* __restrict__ embed, uint4* __restrict__ x_out,
-                                                                 int hidden, uint8_t* __restrict__ seen_prev) {
+// stage 2: one wave per sequence merges the NB partials and applies the token bookkeeping (EX: and counts the emitted token)
+template <bool EX>
+__device__ __forceinline__ void sample_greedy_final_body(const float* __restrict__ part, uint8_t* __restrict__ seen,
+                                                         int* __restrict__ cur_tok, int* __restrict__ finished,
+                                                         int* __restrict__ out_ids, float* __restrict__ margins,
+                                                         const int* __restrict__ eos_ids, int n_eos, int pad_id,
+                                                         int V, int step, int out_stride,
+                                                         const uint4* __restrict__ embed, uint4* __restrict__ x_out,
+                                                         int hidden, uint8_t* __restrict__ seen_prev, const o3v_samp_x& sx) {
     const int b = blockIdx.x, lane = threadIdx.x;
     const float* p = part + ((size_t)b * GREEDY_NB + lane) * 4;
     float best = -INFINITY, second = -INFINITY;
@@ -759,6 +795,7 @@ __global__ __launch_bounds__(64) void sample_greedy_final_kernel(const float* __
     }
     if (lane == 0) {
         int tok = finished[b] ? pad_id : bi;
+        if (EX && sx.counts) o3v_count_token(sx, b, V, tok, finished[b] != 0);
         if (!finished[b]) {
             for (int k = 0; k < n_eos; ++k)
                 if (tok == eos_ids[k]) finished[b] = 1;
@@ -777,17 +814,45 @@ __global__ __launch_bounds__(64) void sample_greedy_final_kernel(const float* __
         for (int c = lane; c < cpr; c += 64) x_out[(size_t)b * cpr + c] = src[c];
     }
 }
+__global__ __launch_bounds__(64) void sample_greedy_final_kernel(const float* __restrict__ part, uint8_t* __restrict__ seen,
+                                                                 int* __restrict__ cur_tok, int* __restrict__ finished,
+                                                                 int* __restrict__ out_ids, float* __restrict__ margins,
+                                                                 const int* __restrict__ eos_ids, int n_eos, int pad_id,
+                                                                 int V, int step, int out_stride,
+                                                                 const uint4* __restrict__ embed, uint4* __restrict__ x_out,
+                                                                 int hidden, uint8_t* __restrict__ seen_prev) {
+    sample_greedy_final_body<false>(part, seen, cur_tok, finished, out_ids, margins, eos_ids, n_eos, pad_id, V, step, out_stride, embed,
+                                    x_out, hidden, seen_prev, o3v_samp_x{});
+}
+__global__ __launch_bounds__(64) void sample_greedy_final_kernel_x(const float* __restrict__ part, uint8_t* __restrict__ seen,
+                                                                   int* __restrict__ cur_tok, int* __restrict__ finished,
+                                                                   int* __restrict__ out_ids, float* __restrict__ margins,
+                                                                   const int* __restrict__ eos_ids, int n_eos, int pad_id,
+                                                                   int V, int step, int out_stride,
+                                                                   const uint4* __restrict__ embed, uint4* __restrict__ x_out,
+                                                                   int hidden, uint8_t* __restrict__ seen_prev, o3v_samp_x sx) {
+    sample_greedy_final_body<true>(part, seen, cur_tok, finished, out_ids, margins, eos_ids, n_eos, pad_id, V, step, out_stride, embed,
+                                   x_out, hidden, seen_prev, sx);
+}
 
 // scratch: f32 [B, 64, 4] partials.  seen_prev (optional, u8 [B]): the chosen token's seen byte before this step sets it
 int o3v_sample_greedy_ex(const void* logits, void* seen, int* cur_tok, int* finished, int* out_ids, float* margins,
                          const int* eos_ids, int n_eos, int pad_id, int B, int V, int ldl, float rep_penalty, int step,
                          int out_stride, float* scratch, const void* embed, void* x_out, int hidden, uint8_t* seen_prev,
-                         hipStream_t stream) {
+                         const o3v_samp_x* sx, hipStream_t stream) {
     if (!logits || !seen || !cur_tok || !finished || !out_ids || !scratch || B < 0 || V <= 0 || step < 0 ||
         step >= out_stride)
         return O3V_ERR_ARG;
     if (embed && (!x_out || hidden <= 0 || (hidden & 7))) return O3V_ERR_ARG;
     if (B == 0) return O3V_OK;
+    if (sx) {
+        O3V_KLAUNCH(sample_greedy_partial_kernel_x, dim3(GREEDY_NB, B), dim3(256), 0, stream, (const bf16_t*)logits,
+                    (const uint8_t*)seen, scratch, V, ldl, rep_penalty, *sx);
+        O3V_KLAUNCH(sample_greedy_final_kernel_x, dim3(B), dim3(64), 0, stream, scratch, (uint8_t*)seen, cur_tok, finished, out_ids,
+                    margins, eos_ids, n_eos, pad_id, V, step, out_stride, (const uint4*)embed, (uint4*)x_out, hidden, seen_prev, *sx);
+        O3V_CHECK_LAUNCH();
+        return O3V_OK;
+    }
     O3V_KLAUNCH(sample_greedy_partial_kernel, dim3(GREEDY_NB, B), dim3(256), 0, stream, (const bf16_t*)logits,
                 (const uint8_t*)seen, scratch, V, ldl, rep_penalty);
     O3V_KLAUNCH(sample_greedy_final_kernel, dim3(B), dim3(64), 0, stream, scratch, (uint8_t*)seen, cur_tok, finished, out_ids,
@@ -800,7 +865,7 @@ extern "C" int o3v_sample_greedy(const void* logits, void* seen, int* cur_tok, i
                                  const int* eos_ids, int n_eos, int pad_id, int B, int V, int ldl, float rep_penalty,
                                  int step, int out_stride, float* scratch, hipStream_t stream) {
     return o3v_sample_greedy_ex(logits, seen, cur_tok, finished, out_ids, margins, eos_ids, n_eos, pad_id, B, V, ldl, rep_penalty,
-                                step, out_stride, scratch, nullptr, nullptr, 0, nullptr, stream);
+                                step, out_stride, scratch, nullptr, nullptr, 0, nullptr, nullptr, stream);
 }
 
 // The same, and the chosen token's embedding row goes to x_out[b] (bf16 [B, hidden]) -- what the next decode forward
@@ -811,7 +876,7 @@ extern "C" int o3v_sample_greedy_embed(const void* logits, void* seen, int* cur_
                                        void* x_out, int hidden, hipStream_t stream) {
     if (!embed) return O3V_ERR_ARG;
     return o3v_sample_greedy_ex(logits, seen, cur_tok, finished, out_ids, margins, eos_ids, n_eos, pad_id, B, V, ldl, rep_penalty,
-                                step, out_stride, scratch, embed, x_out, hidden, nullptr, stream);
+                                step, out_stride, scratch, embed, x_out, hidden, nullptr, nullptr, stream);
 }
 
 // mark prompt ids as seen (repetition penalty covers prompt + generated, TF:logits_process.py:404-414)

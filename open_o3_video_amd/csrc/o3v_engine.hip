@@ -450,7 +450,8 @@ int llm_head(const o3v_llm_desc* d, const void* x, int ldx, int rows, void* norm
 int o3v_sample_lp_step(const void* logits, void* seen, int* cur_tok, int* finished, int* out_ids, float* margins, const int* eos_ids,
                        int n_eos, int pad_id, int B, int V, int ldl, int do_sample, float rep_penalty, float temperature, int top_k,
                        float top_p, uint64_t seed, const int* row_id, int step, int out_stride, float* scratch, const void* embed,
-                       void* x_out, int hidden, const o3v_logprob_opts* lp, hipStream_t stream);
+                       void* x_out, int hidden, const o3v_logprob_opts* lp, const o3v_samp_x* sx, hipStream_t stream);
+int o3v_sampling_resolve(const o3v_sampling_opts* so, int step, o3v_samp_x* x);
 
 extern "C" int o3v_llm_decode(const o3v_llm_desc* d, const o3v_decode_state* st, int step0, int n_steps,
                               int skip_last_forward, o3v_stream_t s) {
@@ -459,6 +460,16 @@ extern "C" int o3v_llm_decode(const o3v_llm_desc* d, const o3v_decode_state* st,
 
 extern "C" int o3v_llm_decode_lp(const o3v_llm_desc* d, const o3v_decode_state* st, const o3v_logprob_opts* lp, int step0,
                                  int n_steps, int skip_last_forward, o3v_stream_t s) {
+    return o3v_llm_decode_ex(d, st, lp, nullptr, step0, n_steps, skip_last_forward, s);
+}
+
+extern "C" int o3v_llm_decode_ex(const o3v_llm_desc* d, const o3v_decode_state* st, const o3v_logprob_opts* lp,
+                                 const o3v_sampling_opts* so, int step0, int n_steps, int skip_last_forward, o3v_stream_t s) {
+    if (so) {  // host-only checks of the controls, before anything else
+        o3v_samp_x probe;
+        const int rc = o3v_sampling_resolve(so, 0, &probe);
+        if (rc != O3V_OK) return rc;
+    }
     if (!d || !st || !st->x || !st->kcache || !st->vcache || !st->cosT || !st->sinT || !st->logits || !st->seen ||
         !st->cur_tok || !st->finished || !st->out_ids || !st->part_o || !st->part_ml || !st->workspace)
         return O3V_ERR_ARG;
@@ -575,11 +586,18 @@ extern "C" int o3v_llm_decode_lp(const o3v_llm_desc* d, const o3v_decode_state* 
     };
     for (int i = 0; i < n_steps; ++i) {
         step = step0 + i;
-        if (lp)  // the same sampler, then the log-probs of what it drew (sampling: the embedding row is gathered below as usual)
+        if (so) {  // the extended sampler kernels on this step's controls, then (lp given) its log-probs
+            o3v_samp_x sx;
+            TRY(o3v_sampling_resolve(so, step, &sx));
             TRY(o3v_sample_lp_step(st->logits, st->seen, st->cur_tok, st->finished, st->out_ids, st->margins, st->eos_ids, st->n_eos,
                                    st->pad_id, B, V, V, st->do_sample, st->rep_penalty, st->temperature, st->top_k, st->top_p, st->seed,
                                    st->row_id, step, st->Tnew, st->sample_scratch, st->do_sample ? nullptr : d->embed, st->x, H, lp,
-                                   s));
+                                   &sx, s));
+        } else if (lp)  // the same sampler, then the log-probs of what it drew (sampling: the embedding row is gathered below as usual)
+            TRY(o3v_sample_lp_step(st->logits, st->seen, st->cur_tok, st->finished, st->out_ids, st->margins, st->eos_ids, st->n_eos,
+                                   st->pad_id, B, V, V, st->do_sample, st->rep_penalty, st->temperature, st->top_k, st->top_p, st->seed,
+                                   st->row_id, step, st->Tnew, st->sample_scratch, st->do_sample ? nullptr : d->embed, st->x, H, lp,
+                                   nullptr, s));
         else if (st->do_sample)
             TRY(o3v_sample_top_k_top_p(st->logits, st->seen, st->cur_tok, st->finished, st->out_ids, st->margins, st->eos_ids,
                                        st->n_eos, st->pad_id, B, V, V, st->rep_penalty, st->temperature, st->top_k, st->top_p,

@@ -19,6 +19,7 @@
 // (SURVEY.md section 8e).
 #include "../../include/o3v.h"
 #include "o3v_common.h"
+#include <string.h>
 
 namespace {
 
@@ -90,16 +91,28 @@ __device__ u64 block_scan_excl_u64(u64 v, u64* red, u64* total) {
     return off + incl - v;
 }
 
+typedef o3v_samp_x SampX;
+
 struct Row {
     const bf16_t* lr;
     const uint8_t* sr;
     int V;
     bool vec;
     float rep, temp;
+    // extended controls (read by the EX instantiations only): static edits f32 [V], the row's output counts u16 [V], penalties
+    const float* bias;
+    const uint16_t* cr;
+    float pres, freq;
 };
 
-__device__ __forceinline__ Row make_row(const bf16_t* logits, const uint8_t* seen, int b, int V, int ldl, float rep, float temp) {
+template <bool EX = false>
+__device__ __forceinline__ Row make_row(const bf16_t* logits, const uint8_t* seen, int b, int V, int ldl, float rep, float temp,
+                                        const SampX& x = SampX{}) {
     Row r;
+    r.bias = EX ? x.bias : nullptr;   // the entry points check their 16-byte alignment, so `vec` below covers them
+    r.cr = (EX && x.counts) ? x.counts + (size_t)b * V : nullptr;
+    r.pres = EX ? x.pres : 0.f;
+    r.freq = EX ? x.freq : 0.f;
     r.lr = logits + (size_t)b * ldl;
     r.sr = seen + (size_t)b * V;
     r.V = V;
@@ -110,17 +123,34 @@ __device__ __forceinline__ Row make_row(const bf16_t* logits, const uint8_t* see
     return r;
 }
 
-// processed scores of elements 8g..8g+7 (TF:404-414 penalty, :301-303 temperature); -inf past the vocabulary
+// presence / frequency penalty of a token this row has emitted c > 0 times (vLLM sampler.py apply_penalties, in fp32)
+__device__ __forceinline__ float count_penalty(float x, unsigned c, float pres, float freq) { return x - (freq * (float)c + pres); }
+
+// processed scores of elements 8g..8g+7 (TF:404-414 penalty, :301-303 temperature); -inf past the vocabulary.
+// EX: the static edits are added first and the count penalties follow the repetition penalty (vLLM 0.7.2 V0 sampler order).
+template <bool EX = false>
 __device__ __forceinline__ void load_group(const Row& r, int g, float s[8]) {
     const int base = g * 8;
     if (r.vec && base + 8 <= r.V) {
         const u32x4 lv = *reinterpret_cast<const u32x4*>(r.lr + base);
         const uint2 sv = *reinterpret_cast<const uint2*>(r.sr + base);
+        float bv[8];
+        u32x4 cv = {0u, 0u, 0u, 0u};
+        if (EX && r.bias) {
+            const float4 b0 = *reinterpret_cast<const float4*>(r.bias + base), b1 = *reinterpret_cast<const float4*>(r.bias + base + 4);
+            bv[0] = b0.x, bv[1] = b0.y, bv[2] = b0.z, bv[3] = b0.w, bv[4] = b1.x, bv[5] = b1.y, bv[6] = b1.z, bv[7] = b1.w;
+        }
+        if (EX && r.cr) cv = *reinterpret_cast<const u32x4*>(r.cr + base);
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
             float x = bf2f((bf16_t)((lv[k >> 1] >> (16 * (k & 1))) & 0xffffu));
             const unsigned sb = ((k < 4 ? sv.x : sv.y) >> (8 * (k & 3))) & 0xffu;
+            if (EX && r.bias) x += bv[k];
             if (r.rep != 1.0f && sb) x = (x < 0.f) ? x * r.rep : x / r.rep;
+            if (EX) {
+                const unsigned c = (cv[k >> 1] >> (16 * (k & 1))) & 0xffffu;
+                if (c) x = count_penalty(x, c, r.pres, r.freq);
+            }
             s[k] = x / r.temp;
         }
     } else {
@@ -130,7 +160,12 @@ __device__ __forceinline__ void load_group(const Row& r, int g, float s[8]) {
             float x = -INFINITY;
             if (i < r.V) {
                 x = bf2f(r.lr[i]);
+                if (EX && r.bias) x += r.bias[i];
                 if (r.rep != 1.0f && r.sr[i]) x = (x < 0.f) ? x * r.rep : x / r.rep;
+                if (EX && r.cr) {
+                    const unsigned c = r.cr[i];
+                    if (c) x = count_penalty(x, c, r.pres, r.freq);
+                }
                 x = x / r.temp;
             }
             s[k] = x;
@@ -139,13 +174,13 @@ __device__ __forceinline__ void load_group(const Row& r, int g, float s[8]) {
 }
 
 // Visits the elements of block `blk`'s slice of the row: thread t owns groups g0+t, g0+t+NT, ...
-template <typename F>
+template <bool EX = false, typename F>
 __device__ __forceinline__ void for_each_score(const Row& r, int blk, F&& f) {
     const int NG = (r.V + 7) / 8, per_blk = (NG + NBLK - 1) / NBLK;
     const int g0 = blk * per_blk, g1 = (g0 + per_blk < NG) ? g0 + per_blk : NG;
     for (int g = g0 + threadIdx.x; g < g1; g += NT) {
         float s[8];
-        load_group(r, g, s);
+        load_group<EX>(r, g, s);
 #pragma unroll
         for (int k = 0; k < 8; ++k) f(g * 8 + k, s[k]);
     }
@@ -213,24 +248,36 @@ __device__ int pick_bin(const u64* __restrict__ hist, int nb, u64 cut, u64* belo
 }
 
 // K1: slice maxima of the processed scores; clears the row's accumulators for the kernels that follow
-__global__ __launch_bounds__(NT) void sample_max_kernel(const bf16_t* __restrict__ logits, const uint8_t* __restrict__ seen,
-                                                        u64* __restrict__ wsp, int V, int ldl, float rep, float temp) {
+// Every kernel below is a body templated on EX with two entry points: the plain one (EX false: the sampler as it always was)
+// and `_x` (EX true: static edits, count penalties and min_p of o3v_sampling_opts feeding the same passes).
+template <bool EX>
+__device__ __forceinline__ void sample_max_body(const bf16_t* __restrict__ logits, const uint8_t* __restrict__ seen,
+                                                u64* __restrict__ wsp, int V, int ldl, float rep, float temp, const SampX& x) {
     __shared__ float redf[NT / 64];
     const int blk = blockIdx.x, b = blockIdx.y;
     u64* ws = wsp + (size_t)b * (WS_FLOATS / 2);
-    const Row r = make_row(logits, seen, b, V, ldl, rep, temp);
+    const Row r = make_row<EX>(logits, seen, b, V, ldl, rep, temp, x);
     for (int i = blk * NT + threadIdx.x; i < WS_PMAX; i += NBLK * NT) ws[i] = 0;
     float mx = -INFINITY;
-    for_each_score(r, blk, [&](int, float s) { mx = fmaxf(mx, s); });
+    for_each_score<EX>(r, blk, [&](int, float s) { mx = fmaxf(mx, s); });
     mx = block_max(mx, redf);
     if (threadIdx.x == 0) reinterpret_cast<float*>(ws + WS_PMAX)[blk] = mx;
+}
+__global__ __launch_bounds__(NT) void sample_max_kernel(const bf16_t* __restrict__ logits, const uint8_t* __restrict__ seen,
+                                                        u64* __restrict__ wsp, int V, int ldl, float rep, float temp) {
+    sample_max_body<false>(logits, seen, wsp, V, ldl, rep, temp, SampX{});
+}
+__global__ __launch_bounds__(NT) void sample_max_kernel_x(const bf16_t* __restrict__ logits, const uint8_t* __restrict__ seen,
+                                                          u64* __restrict__ wsp, int V, int ldl, float rep, float temp, SampX x) {
+    sample_max_body<true>(logits, seen, wsp, V, ldl, rep, temp, x);
 }
 
 // top-k, levels 0..2: histogram of COUNTS over 12 / 12 / 8 bits of the inverted key (bin 0 = largest scores), restricted to
 // the bins the earlier levels chose for the k-th largest element
-template <int LVL>
-__global__ __launch_bounds__(NT) void sample_count_kernel(const bf16_t* __restrict__ logits, const uint8_t* __restrict__ seen,
-                                                          u64* __restrict__ wsp, int V, int ldl, float rep, float temp, int top_k) {
+template <int LVL, bool EX>
+__device__ __forceinline__ void sample_count_body(const bf16_t* __restrict__ logits, const uint8_t* __restrict__ seen,
+                                                  u64* __restrict__ wsp, int V, int ldl, float rep, float temp, int top_k,
+                                                  const SampX& x) {
     constexpr int SH = LVL == 0 ? 20 : (LVL == 1 ? 8 : 0), NB = LVL == 2 ? 256 : 4096;
     __shared__ unsigned hist[NB];
     __shared__ u64 red[NT / 64];
@@ -238,7 +285,7 @@ __global__ __launch_bounds__(NT) void sample_count_kernel(const bf16_t* __restri
     __shared__ u64 s_below;
     const int blk = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
     u64* ws = wsp + (size_t)b * (WS_FLOATS / 2);
-    const Row r = make_row(logits, seen, b, V, ldl, rep, temp);
+    const Row r = make_row<EX>(logits, seen, b, V, ldl, rep, temp, x);
     for (int i = tid; i < NB; i += NT) hist[i] = 0;
     unsigned prefix = 0, hi_mask = 0;
     if (LVL > 0) {
@@ -252,7 +299,7 @@ __global__ __launch_bounds__(NT) void sample_count_kernel(const bf16_t* __restri
         }
     }
     __syncthreads();
-    for_each_score(r, blk, [&](int i, float s) {
+    for_each_score<EX>(r, blk, [&](int i, float s) {
         if (i >= V) return;
         const unsigned inv = ~score_key(s);
         if ((inv & hi_mask) == prefix) atomicAdd(&hist[(inv >> SH) & (NB - 1)], 1u);
@@ -261,6 +308,17 @@ __global__ __launch_bounds__(NT) void sample_count_kernel(const bf16_t* __restri
     u64* gh = ws + (LVL == 0 ? WS_C0 : (LVL == 1 ? WS_C1 : WS_C2));
     for (int i = tid; i < NB; i += NT)
         if (hist[i]) atomicAdd(gh + i, (u64)hist[i]);
+}
+template <int LVL>
+__global__ __launch_bounds__(NT) void sample_count_kernel(const bf16_t* __restrict__ logits, const uint8_t* __restrict__ seen,
+                                                          u64* __restrict__ wsp, int V, int ldl, float rep, float temp, int top_k) {
+    sample_count_body<LVL, false>(logits, seen, wsp, V, ldl, rep, temp, top_k, SampX{});
+}
+template <int LVL>
+__global__ __launch_bounds__(NT) void sample_count_kernel_x(const bf16_t* __restrict__ logits, const uint8_t* __restrict__ seen,
+                                                            u64* __restrict__ wsp, int V, int ldl, float rep, float temp, int top_k,
+                                                            SampX x) {
+    sample_count_body<LVL, true>(logits, seen, wsp, V, ldl, rep, temp, top_k, x);
 }
 
 // top-k: one block per row resolves the key of the k-th largest score (fewer than k scores: the smallest one)
@@ -280,10 +338,10 @@ __global__ __launch_bounds__(NT) void sample_kth_kernel(u64* __restrict__ wsp, i
 // K2..K4 (LVL 0,1,2): mass histogram over 12 / 12 / 7 bits of e = exp(s - max) for the elements that match the bits
 // decided by the earlier levels.  Radix select of the smallest tau with mass{e <= tau} > (1 - top_p) z: the kept set
 // is {e >= tau} (TF keeps the complement of the ascending prefix with cumulative probability <= 1 - top_p).
-template <int LVL>
-__global__ __launch_bounds__(NT) void sample_hist_kernel(const bf16_t* __restrict__ logits, const uint8_t* __restrict__ seen,
-                                                         u64* __restrict__ wsp, int V, int ldl, float rep, float temp,
-                                                         float top_p) {
+template <int LVL, bool EX>
+__device__ __forceinline__ void sample_hist_body(const bf16_t* __restrict__ logits, const uint8_t* __restrict__ seen,
+                                                 u64* __restrict__ wsp, int V, int ldl, float rep, float temp, float top_p,
+                                                 const SampX& x) {
     constexpr int SH = LVL == 0 ? 19 : (LVL == 1 ? 7 : 0), NB = LVL == 2 ? 128 : 4096;
     __shared__ u64 hist[NB];
     __shared__ u64 red[NT / 64];
@@ -291,7 +349,7 @@ __global__ __launch_bounds__(NT) void sample_hist_kernel(const bf16_t* __restric
     __shared__ u64 s_below;
     const int blk = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
     u64* ws = wsp + (size_t)b * (WS_FLOATS / 2);
-    const Row r = make_row(logits, seen, b, V, ldl, rep, temp);
+    const Row r = make_row<EX>(logits, seen, b, V, ldl, rep, temp, x);
     const float mx = row_max(ws);
     for (int i = tid; i < NB; i += NT) hist[i] = 0;
     unsigned prefix = 0, hi_mask = 0;
@@ -308,7 +366,7 @@ __global__ __launch_bounds__(NT) void sample_hist_kernel(const bf16_t* __restric
     __syncthreads();
     u64 zsum = 0;
     const unsigned kth = (unsigned)ws[WS_KTH];
-    for_each_score(r, blk, [&](int, float s) {
+    for_each_score<EX>(r, blk, [&](int, float s) {
         if (score_key(s) < kth) return;   // removed by top-k
         const float e = expf(s - mx);
         const u64 fx = to_fx(e);
@@ -325,17 +383,32 @@ __global__ __launch_bounds__(NT) void sample_hist_kernel(const bf16_t* __restric
     for (int i = tid; i < NB; i += NT)
         if (hist[i]) atomicAdd(gh + i, hist[i]);
 }
-
-// K5: kept mass {bits(e) >= tau} of every slice; publishes tau (all blocks of a row compute the same value)
-__global__ __launch_bounds__(NT) void sample_mass_kernel(const bf16_t* __restrict__ logits, const uint8_t* __restrict__ seen,
+template <int LVL>
+__global__ __launch_bounds__(NT) void sample_hist_kernel(const bf16_t* __restrict__ logits, const uint8_t* __restrict__ seen,
                                                          u64* __restrict__ wsp, int V, int ldl, float rep, float temp,
                                                          float top_p) {
+    sample_hist_body<LVL, false>(logits, seen, wsp, V, ldl, rep, temp, top_p, SampX{});
+}
+template <int LVL>
+__global__ __launch_bounds__(NT) void sample_hist_kernel_x(const bf16_t* __restrict__ logits, const uint8_t* __restrict__ seen,
+                                                           u64* __restrict__ wsp, int V, int ldl, float rep, float temp,
+                                                           float top_p, SampX x) {
+    sample_hist_body<LVL, true>(logits, seen, wsp, V, ldl, rep, temp, top_p, x);
+}
+
+// K5: kept mass {bits(e) >= tau} of every slice; publishes tau (all blocks of a row compute the same value).
+// EX: min_p (vLLM sampler.py _apply_min_p: drop probs < min_p * max prob, i.e. e < min_p) raises tau to at least bits(min_p); the
+// draw and the log-prob kernels read the published tau, so they need no min_p of their own.
+template <bool EX>
+__device__ __forceinline__ void sample_mass_body(const bf16_t* __restrict__ logits, const uint8_t* __restrict__ seen,
+                                                 u64* __restrict__ wsp, int V, int ldl, float rep, float temp, float top_p,
+                                                 const SampX& x) {
     __shared__ u64 red[NT / 64];
     __shared__ int s_pick;
     __shared__ u64 s_below;
     const int blk = blockIdx.x, b = blockIdx.y;
     u64* ws = wsp + (size_t)b * (WS_FLOATS / 2);
-    const Row r = make_row(logits, seen, b, V, ldl, rep, temp);
+    const Row r = make_row<EX>(logits, seen, b, V, ldl, rep, temp, x);
     const float mx = row_max(ws);
     unsigned prefix = 0;
     if (top_p < 1.0f) {
@@ -345,9 +418,10 @@ __global__ __launch_bounds__(NT) void sample_mass_kernel(const bf16_t* __restric
         prefix |= (unsigned)pick_bin(ws + WS_H1, 4096, cut, &below, red, &s_pick, &s_below) << 7;
         prefix |= (unsigned)pick_bin(ws + WS_H2, 128, cut, &below, red, &s_pick, &s_below);
     }
+    if (EX && x.minp_bits > prefix) prefix = x.minp_bits;
     u64 mine = 0;
     const unsigned kth = (unsigned)ws[WS_KTH];
-    for_each_score(r, blk, [&](int, float s) {
+    for_each_score<EX>(r, blk, [&](int, float s) {
         const float e = expf(s - mx);
         if (score_key(s) >= kth && __float_as_uint(e) >= prefix) mine += to_fx(e);
     });
@@ -357,16 +431,28 @@ __global__ __launch_bounds__(NT) void sample_mass_kernel(const bf16_t* __restric
         ws[WS_PREFIX] = prefix;
     }
 }
+__global__ __launch_bounds__(NT) void sample_mass_kernel(const bf16_t* __restrict__ logits, const uint8_t* __restrict__ seen,
+                                                         u64* __restrict__ wsp, int V, int ldl, float rep, float temp,
+                                                         float top_p) {
+    sample_mass_body<false>(logits, seen, wsp, V, ldl, rep, temp, top_p, SampX{});
+}
+__global__ __launch_bounds__(NT) void sample_mass_kernel_x(const bf16_t* __restrict__ logits, const uint8_t* __restrict__ seen,
+                                                           u64* __restrict__ wsp, int V, int ldl, float rep, float temp,
+                                                           float top_p, SampX x) {
+    sample_mass_body<true>(logits, seen, wsp, V, ldl, rep, temp, top_p, x);
+}
 
 // K6: the draw.  Elements are ordered by slice, then by owning thread, then by that thread's visiting order; the block
 // and then the thread whose mass range holds the target walk to the token.
-__global__ __launch_bounds__(NT) void sample_draw_kernel(const bf16_t* __restrict__ logits, uint8_t* __restrict__ seen,
-                                                         const u64* __restrict__ wsp, int* __restrict__ cur_tok,
-                                                         int* __restrict__ finished, int* __restrict__ out_ids,
-                                                         float* __restrict__ chosen_lp, const int* __restrict__ eos_ids,
-                                                         int n_eos, int pad_id, int V, int ldl, float rep, float temp,
-                                                         uint64_t seed, const int* __restrict__ row_id, int step,
-                                                         int out_stride, uint8_t* __restrict__ seen_prev) {
+// EX: the emitted token of an unfinished row is counted (u16, saturating); its count before the step goes to cnt_prev.
+template <bool EX>
+__device__ __forceinline__ void sample_draw_body(const bf16_t* __restrict__ logits, uint8_t* __restrict__ seen,
+                                                 const u64* __restrict__ wsp, int* __restrict__ cur_tok,
+                                                 int* __restrict__ finished, int* __restrict__ out_ids,
+                                                 float* __restrict__ chosen_lp, const int* __restrict__ eos_ids,
+                                                 int n_eos, int pad_id, int V, int ldl, float rep, float temp,
+                                                 uint64_t seed, const int* __restrict__ row_id, int step,
+                                                 int out_stride, uint8_t* __restrict__ seen_prev, const SampX& x) {
     __shared__ u64 red[NT / 64];
     const int blk = blockIdx.x, b = blockIdx.y;
     const u64* ws = wsp + (size_t)b * (WS_FLOATS / 2);
@@ -382,11 +468,11 @@ __global__ __launch_bounds__(NT) void sample_draw_kernel(const bf16_t* __restric
     if (tot > 0 && target >= tot) target = tot - 1;
     const u64 blk_mass = ws[WS_BM + blk];
     if (!(blk_mass > 0 && blk_before <= target && target < blk_before + blk_mass)) return;  // block-uniform
-    const Row r = make_row(logits, seen, b, V, ldl, rep, temp);
+    const Row r = make_row<EX>(logits, seen, b, V, ldl, rep, temp, x);
     const float mx = row_max(ws);
     const unsigned prefix = (unsigned)ws[WS_PREFIX], kth = (unsigned)ws[WS_KTH];
     u64 mine = 0;
-    for_each_score(r, blk, [&](int, float s) {
+    for_each_score<EX>(r, blk, [&](int, float s) {
         const float e = expf(s - mx);
         if (score_key(s) >= kth && __float_as_uint(e) >= prefix) mine += to_fx(e);
     });
@@ -396,7 +482,7 @@ __global__ __launch_bounds__(NT) void sample_draw_kernel(const bf16_t* __restric
         u64 run = before;
         int pick = -1;
         float e_pick = 0.f;
-        for_each_score(r, blk, [&](int i, float s) {
+        for_each_score<EX>(r, blk, [&](int i, float s) {
             if (pick >= 0) return;
             const float e = expf(s - mx);
             if (score_key(s) >= kth && __float_as_uint(e) >= prefix) {
@@ -414,10 +500,31 @@ __global__ __launch_bounds__(NT) void sample_draw_kernel(const bf16_t* __restric
                 if (tok == eos_ids[k]) finished[b] = 1;
         if (seen_prev) seen_prev[b] = (tok >= 0 && tok < V) ? seen[(size_t)b * V + tok] : 0;  // log-probs see the map before this step
         if (tok >= 0 && tok < V) seen[(size_t)b * V + tok] = 1;
+        if (EX && x.counts) o3v_count_token(x, b, V, tok, fin);
         cur_tok[b] = tok;
         out_ids[(size_t)b * out_stride + step] = tok;
         if (chosen_lp) chosen_lp[(size_t)b * out_stride + step] = logf(e_pick / ((float)ws[WS_Z] * (1.0f / FX_SCALE)));
     }
+}
+__global__ __launch_bounds__(NT) void sample_draw_kernel(const bf16_t* __restrict__ logits, uint8_t* __restrict__ seen,
+                                                         const u64* __restrict__ wsp, int* __restrict__ cur_tok,
+                                                         int* __restrict__ finished, int* __restrict__ out_ids,
+                                                         float* __restrict__ chosen_lp, const int* __restrict__ eos_ids,
+                                                         int n_eos, int pad_id, int V, int ldl, float rep, float temp,
+                                                         uint64_t seed, const int* __restrict__ row_id, int step,
+                                                         int out_stride, uint8_t* __restrict__ seen_prev) {
+    sample_draw_body<false>(logits, seen, wsp, cur_tok, finished, out_ids, chosen_lp, eos_ids, n_eos, pad_id, V, ldl, rep, temp, seed,
+                            row_id, step, out_stride, seen_prev, SampX{});
+}
+__global__ __launch_bounds__(NT) void sample_draw_kernel_x(const bf16_t* __restrict__ logits, uint8_t* __restrict__ seen,
+                                                           const u64* __restrict__ wsp, int* __restrict__ cur_tok,
+                                                           int* __restrict__ finished, int* __restrict__ out_ids,
+                                                           float* __restrict__ chosen_lp, const int* __restrict__ eos_ids,
+                                                           int n_eos, int pad_id, int V, int ldl, float rep, float temp,
+                                                           uint64_t seed, const int* __restrict__ row_id, int step,
+                                                           int out_stride, uint8_t* __restrict__ seen_prev, SampX x) {
+    sample_draw_body<true>(logits, seen, wsp, cur_tok, finished, out_ids, chosen_lp, eos_ids, n_eos, pad_id, V, ldl, rep, temp, seed,
+                           row_id, step, out_stride, seen_prev, x);
 }
 
 
@@ -440,8 +547,9 @@ constexpr int LP_MAXN = 20;                              // O3V_MAX_LOGPROBS
 constexpr int LP_REC = 24;                               // u64 per slice record: LP_MAXN keys, greater-count, {max, sum}
 constexpr int LP_OFF = 18432;                            // u64 offset of a row's records inside its sampler scratch row
 constexpr int LP_SEEN_PREV = LP_OFF + NBLK * LP_REC;     // row 0 only: u8 [B <= 32] chosen tokens' seen bytes before the step
+constexpr int LP_CNT_PREV = LP_SEEN_PREV + 4;            // row 0 only: u16 [B <= 32] chosen tokens' output counts before the step
 constexpr int LP_NB_ROWS = 8;                            // slices per row of the prompt-side entry (many rows in flight)
-static_assert(WS_U64 <= LP_OFF && LP_SEEN_PREV + 4 <= WS_FLOATS / 2, "log-prob records inside the sampler scratch row");
+static_assert(WS_U64 <= LP_OFF && LP_CNT_PREV + 8 <= WS_FLOATS / 2, "log-prob records inside the sampler scratch row");
 static_assert(LP_NB_ROWS * LP_REC * 2 == 384, "O3V_LOGPROB_ROW_SCRATCH_FLOATS");
 
 __device__ __forceinline__ u64 shfl_u64(u64 v, int src) {
@@ -488,11 +596,18 @@ struct WaveTopN {
 };
 
 // score of the chosen / target token under the state it was drawn in (seen_prev NULL: raw logits, the prompt side)
+// EX: with the static edits and the token's count as it was before the step counted it (cnt_prev)
+template <bool EX = false>
 __device__ __forceinline__ float lp_token_score(const bf16_t* lr, int tok, int V, const uint8_t* seen_prev, int b, float rep,
-                                                float temp) {
+                                                float temp, const SampX& sx = SampX{}) {
     if (tok < 0 || tok >= V) return -INFINITY;
     float x = bf2f(lr[tok]);
+    if (EX && sx.bias) x += sx.bias[tok];
     if (seen_prev && rep != 1.0f && seen_prev[b]) x = (x < 0.f) ? x * rep : x / rep;
+    if (EX && sx.counts && sx.cnt_prev) {
+        const unsigned c = sx.cnt_prev[b];
+        if (c) x = count_penalty(x, c, sx.pres, sx.freq);
+    }
     return x / temp;
 }
 
@@ -506,11 +621,11 @@ struct KeptTest {
     }
 };
 
-template <bool SAMPLED>
-__global__ __launch_bounds__(NT) void lp_partial_kernel(const bf16_t* __restrict__ logits, const uint8_t* __restrict__ seen,
-                                                        const u64* __restrict__ wsp, u64* __restrict__ recp, int rec_stride, int nblk,
-                                                        const int* __restrict__ tok_arr, const uint8_t* __restrict__ seen_prev, int V,
-                                                        int ldl, float rep, float temp, int n) {
+template <bool SAMPLED, bool EX>
+__device__ __forceinline__ void lp_partial_body(const bf16_t* __restrict__ logits, const uint8_t* __restrict__ seen,
+                                                const u64* __restrict__ wsp, u64* __restrict__ recp, int rec_stride, int nblk,
+                                                const int* __restrict__ tok_arr, const uint8_t* __restrict__ seen_prev, int V,
+                                                int ldl, float rep, float temp, int n, const SampX& sx) {
     __shared__ u64 s_keys[NT / 64][LP_MAXN];
     __shared__ float s_m[NT / 64], s_z[NT / 64];
     __shared__ unsigned s_c[NT / 64];
@@ -523,13 +638,17 @@ __global__ __launch_bounds__(NT) void lp_partial_kernel(const bf16_t* __restrict
             ((reinterpret_cast<uintptr_t>(seen) & 7) == 0);
     r.rep = rep;
     r.temp = temp;
+    r.bias = EX ? sx.bias : nullptr;
+    r.cr = (EX && sx.counts) ? sx.counts + (size_t)b * V : nullptr;
+    r.pres = EX ? sx.pres : 0.f;
+    r.freq = EX ? sx.freq : 0.f;
     KeptTest kept_test{0.f, 0u, 0u};
     if (SAMPLED) {
         const u64* ws = wsp + (size_t)b * (WS_FLOATS / 2);
         kept_test = KeptTest{row_max(ws), (unsigned)ws[WS_KTH], (unsigned)ws[WS_PREFIX]};
     }
     const int tok = tok_arr[b];
-    const float s_tok = lp_token_score(r.lr, tok, V, seen_prev, b, rep, temp);
+    const float s_tok = lp_token_score<EX>(r.lr, tok, V, seen_prev, b, rep, temp, sx);
     WaveTopN top(n);
     unsigned cnt = 0;
     float m = -INFINITY, z = 0.f;
@@ -540,7 +659,7 @@ __global__ __launch_bounds__(NT) void lp_partial_kernel(const bf16_t* __restrict
         float s[8];
         if (g < g1) {
             if (r.sr) {
-                load_group(r, g, s);  // the sampler's own arithmetic
+                load_group<EX>(r, g, s);  // the sampler's own arithmetic
             } else if (r.vec) {
                 const u32x4 lv = *reinterpret_cast<const u32x4*>(r.lr + g * 8);
 #pragma unroll
@@ -557,6 +676,7 @@ __global__ __launch_bounds__(NT) void lp_partial_kernel(const bf16_t* __restrict
             const float sk = (i == tok) ? s_tok : s[k];  // the chosen token as it was drawn (its seen byte has changed since)
             bool kept = valid;
             if (SAMPLED) kept = kept && kept_test(sk);
+            if (EX) kept = kept && sk > -INFINITY;  // a token the static edits removed is masked, whatever the thresholds say
             cnt += (kept && sk > s_tok) ? 1u : 0u;
             if (!SAMPLED && valid && sk > -INFINITY) {
                 if (sk > m) {
@@ -597,14 +717,28 @@ __global__ __launch_bounds__(NT) void lp_partial_kernel(const bf16_t* __restrict
         mz[1] = z;
     }
 }
-
 template <bool SAMPLED>
-__global__ __launch_bounds__(64) void lp_final_kernel(const bf16_t* __restrict__ logits, const u64* __restrict__ wsp,
-                                                      const u64* __restrict__ recp, int rec_stride, int nblk,
-                                                      const int* __restrict__ tok_arr, const uint8_t* __restrict__ seen_prev, int V,
-                                                      int ldl, float rep, float temp, int n, float* __restrict__ chosen_lp,
-                                                      int* __restrict__ chosen_rank, int* __restrict__ top_ids,
-                                                      float* __restrict__ top_lp, int out_stride, int col) {
+__global__ __launch_bounds__(NT) void lp_partial_kernel(const bf16_t* __restrict__ logits, const uint8_t* __restrict__ seen,
+                                                        const u64* __restrict__ wsp, u64* __restrict__ recp, int rec_stride, int nblk,
+                                                        const int* __restrict__ tok_arr, const uint8_t* __restrict__ seen_prev, int V,
+                                                        int ldl, float rep, float temp, int n) {
+    lp_partial_body<SAMPLED, false>(logits, seen, wsp, recp, rec_stride, nblk, tok_arr, seen_prev, V, ldl, rep, temp, n, SampX{});
+}
+template <bool SAMPLED>
+__global__ __launch_bounds__(NT) void lp_partial_kernel_x(const bf16_t* __restrict__ logits, const uint8_t* __restrict__ seen,
+                                                          const u64* __restrict__ wsp, u64* __restrict__ recp, int rec_stride, int nblk,
+                                                          const int* __restrict__ tok_arr, const uint8_t* __restrict__ seen_prev, int V,
+                                                          int ldl, float rep, float temp, int n, SampX sx) {
+    lp_partial_body<SAMPLED, true>(logits, seen, wsp, recp, rec_stride, nblk, tok_arr, seen_prev, V, ldl, rep, temp, n, sx);
+}
+
+template <bool SAMPLED, bool EX>
+__device__ __forceinline__ void lp_final_body(const bf16_t* __restrict__ logits, const u64* __restrict__ wsp,
+                                              const u64* __restrict__ recp, int rec_stride, int nblk,
+                                              const int* __restrict__ tok_arr, const uint8_t* __restrict__ seen_prev, int V,
+                                              int ldl, float rep, float temp, int n, float* __restrict__ chosen_lp,
+                                              int* __restrict__ chosen_rank, int* __restrict__ top_ids,
+                                              float* __restrict__ top_lp, int out_stride, int col, const SampX& sx) {
     __shared__ int s_ids[LP_MAXN];
     const int b = blockIdx.x, lane = threadIdx.x;
     const u64* rec0 = recp + (size_t)b * rec_stride;
@@ -642,7 +776,7 @@ __global__ __launch_bounds__(64) void lp_final_kernel(const bf16_t* __restrict__
     auto logprob = [&](float s) { return SAMPLED ? (s - kept_test.mx) - lmass : s - lse; };
     const size_t pos = (size_t)b * out_stride + col;
     const int tok = tok_arr[b];
-    const float s_tok = lp_token_score(logits + (size_t)b * ldl, tok, V, seen_prev, b, rep, temp);
+    const float s_tok = lp_token_score<EX>(logits + (size_t)b * ldl, tok, V, seen_prev, b, rep, temp, sx);
     const bool tok_kept = tok >= 0 && tok < V && (!SAMPLED || kept_test(s_tok));
     if (lane == 0) {
         chosen_lp[pos] = tok_kept ? logprob(s_tok) : -INFINITY;
@@ -672,13 +806,33 @@ __global__ __launch_bounds__(64) void lp_final_kernel(const bf16_t* __restrict__
         }
     }
 }
+template <bool SAMPLED>
+__global__ __launch_bounds__(64) void lp_final_kernel(const bf16_t* __restrict__ logits, const u64* __restrict__ wsp,
+                                                      const u64* __restrict__ recp, int rec_stride, int nblk,
+                                                      const int* __restrict__ tok_arr, const uint8_t* __restrict__ seen_prev, int V,
+                                                      int ldl, float rep, float temp, int n, float* __restrict__ chosen_lp,
+                                                      int* __restrict__ chosen_rank, int* __restrict__ top_ids,
+                                                      float* __restrict__ top_lp, int out_stride, int col) {
+    lp_final_body<SAMPLED, false>(logits, wsp, recp, rec_stride, nblk, tok_arr, seen_prev, V, ldl, rep, temp, n, chosen_lp, chosen_rank,
+                                  top_ids, top_lp, out_stride, col, SampX{});
+}
+template <bool SAMPLED>
+__global__ __launch_bounds__(64) void lp_final_kernel_x(const bf16_t* __restrict__ logits, const u64* __restrict__ wsp,
+                                                        const u64* __restrict__ recp, int rec_stride, int nblk,
+                                                        const int* __restrict__ tok_arr, const uint8_t* __restrict__ seen_prev, int V,
+                                                        int ldl, float rep, float temp, int n, float* __restrict__ chosen_lp,
+                                                        int* __restrict__ chosen_rank, int* __restrict__ top_ids,
+                                                        float* __restrict__ top_lp, int out_stride, int col, SampX sx) {
+    lp_final_body<SAMPLED, true>(logits, wsp, recp, rec_stride, nblk, tok_arr, seen_prev, V, ldl, rep, temp, n, chosen_lp, chosen_rank,
+                                 top_ids, top_lp, out_stride, col, sx);
+}
 
 }  // namespace
 
 int o3v_sample_top_k_top_p_ex(const void* logits, void* seen, int* cur_tok, int* finished, int* out_ids, float* chosen_logprob,
                                const int* eos_ids, int n_eos, int pad_id, int B, int V, int ldl, float rep_penalty, float temperature,
                                int top_k, float top_p, uint64_t seed, const int* row_id, int step, int out_stride, float* scratch,
-                               uint8_t* seen_prev, hipStream_t stream) {
+                               uint8_t* seen_prev, const o3v_samp_x* sx, hipStream_t stream) {
     if (!logits || !seen || !cur_tok || !finished || !out_ids || !scratch || B < 0 || V <= 0 || step < 0 ||
         step >= out_stride || !(temperature > 0.f) || !(top_p > 0.f) || top_k < 0 || (reinterpret_cast<uintptr_t>(scratch) & 7))
         return O3V_ERR_ARG;
@@ -687,6 +841,26 @@ int o3v_sample_top_k_top_p_ex(const void* logits, void* seen, int* cur_tok, int*
     uint8_t* sn = (uint8_t*)seen;
     u64* ws = (u64*)scratch;
     const dim3 grid(NBLK, B), block(NT);
+    if (sx) {  // the same passes on the extended row: no added launch
+        const SampX x = *sx;
+        O3V_KLAUNCH(sample_max_kernel_x, grid, block, 0, stream, lg, sn, ws, V, ldl, rep_penalty, temperature, x);
+        if (top_k > 0 && top_k < V) {
+            O3V_KLAUNCH((sample_count_kernel_x<0>), grid, block, 0, stream, lg, sn, ws, V, ldl, rep_penalty, temperature, top_k, x);
+            O3V_KLAUNCH((sample_count_kernel_x<1>), grid, block, 0, stream, lg, sn, ws, V, ldl, rep_penalty, temperature, top_k, x);
+            O3V_KLAUNCH((sample_count_kernel_x<2>), grid, block, 0, stream, lg, sn, ws, V, ldl, rep_penalty, temperature, top_k, x);
+            O3V_KLAUNCH(sample_kth_kernel, dim3(B), block, 0, stream, ws, top_k);
+        }
+        O3V_KLAUNCH((sample_hist_kernel_x<0>), grid, block, 0, stream, lg, sn, ws, V, ldl, rep_penalty, temperature, top_p, x);
+        if (top_p < 1.0f) {
+            O3V_KLAUNCH((sample_hist_kernel_x<1>), grid, block, 0, stream, lg, sn, ws, V, ldl, rep_penalty, temperature, top_p, x);
+            O3V_KLAUNCH((sample_hist_kernel_x<2>), grid, block, 0, stream, lg, sn, ws, V, ldl, rep_penalty, temperature, top_p, x);
+        }
+        O3V_KLAUNCH(sample_mass_kernel_x, grid, block, 0, stream, lg, sn, ws, V, ldl, rep_penalty, temperature, top_p, x);
+        O3V_KLAUNCH(sample_draw_kernel_x, grid, block, 0, stream, lg, sn, ws, cur_tok, finished, out_ids, chosen_logprob, eos_ids,
+                    n_eos, pad_id, V, ldl, rep_penalty, temperature, seed, row_id, step, out_stride, seen_prev, x);
+        O3V_CHECK_LAUNCH();
+        return O3V_OK;
+    }
     O3V_KLAUNCH(sample_max_kernel, grid, block, 0, stream, lg, sn, ws, V, ldl, rep_penalty, temperature);
     if (top_k > 0 && top_k < V) {  // TF:591: top_k = min(top_k, vocabulary); k == V removes nothing
         O3V_KLAUNCH((sample_count_kernel<0>), grid, block, 0, stream, lg, sn, ws, V, ldl, rep_penalty, temperature, top_k);
@@ -711,7 +885,8 @@ extern "C" int o3v_sample_top_k_top_p(const void* logits, void* seen, int* cur_t
                                       float rep_penalty, float temperature, int top_k, float top_p, uint64_t seed,
                                       const int* row_id, int step, int out_stride, float* scratch, hipStream_t stream) {
     return o3v_sample_top_k_top_p_ex(logits, seen, cur_tok, finished, out_ids, chosen_logprob, eos_ids, n_eos, pad_id, B, V, ldl,
-                                     rep_penalty, temperature, top_k, top_p, seed, row_id, step, out_stride, scratch, nullptr, stream);
+                                     rep_penalty, temperature, top_k, top_p, seed, row_id, step, out_stride, scratch, nullptr, nullptr,
+                                     stream);
 }
 
 extern "C" int o3v_sample_top_p(const void* logits, void* seen, int* cur_tok, int* finished, int* out_ids,
@@ -724,43 +899,58 @@ extern "C" int o3v_sample_top_p(const void* logits, void* seen, int* cur_tok, in
 
 // One decode step's sampler exactly as o3v_llm_decode runs it (greedy: penalty + argmax, the embedding row gathered when `embed` is
 // given; sampling: the top-k / top-p passes), then the two log-prob launches.  scratch: f32 [B, O3V_SAMPLE_SCRATCH_FLOATS] in both
-// modes (the log-prob records sit above what either sampler uses).
+// modes (the log-prob records sit above what either sampler uses).  sx (optional): the extended controls of this step -- the `_x`
+// kernels then, and lp may be NULL (no log-prob launches).
 int o3v_sample_lp_step(const void* logits, void* seen, int* cur_tok, int* finished, int* out_ids, float* margins, const int* eos_ids,
                        int n_eos, int pad_id, int B, int V, int ldl, int do_sample, float rep_penalty, float temperature, int top_k,
                        float top_p, uint64_t seed, const int* row_id, int step, int out_stride, float* scratch, const void* embed,
-                       void* x_out, int hidden, const o3v_logprob_opts* lp, hipStream_t stream) {
-    if (!lp || lp->n < 0 || lp->n > LP_MAXN || !lp->chosen_lp || !lp->chosen_rank || (lp->n > 0 && (!lp->top_ids || !lp->top_lp)) ||
-        !scratch || (reinterpret_cast<uintptr_t>(scratch) & 7) || B > 32 || ldl < V)
+                       void* x_out, int hidden, const o3v_logprob_opts* lp, const o3v_samp_x* sx, hipStream_t stream) {
+    if ((!lp && !sx) || !scratch || (reinterpret_cast<uintptr_t>(scratch) & 7) || B > 32 || ldl < V) return O3V_ERR_ARG;
+    if (lp && (lp->n < 0 || lp->n > LP_MAXN || !lp->chosen_lp || !lp->chosen_rank || (lp->n > 0 && (!lp->top_ids || !lp->top_lp))))
         return O3V_ERR_ARG;
     u64* ws = (u64*)scratch;
     uint8_t* seen_prev = reinterpret_cast<uint8_t*>(ws + LP_SEEN_PREV);
+    SampX x{};
+    if (sx) {
+        x = *sx;
+        x.cnt_prev = reinterpret_cast<uint16_t*>(ws + LP_CNT_PREV);
+    }
     if (do_sample) {
         const int rc = o3v_sample_top_k_top_p_ex(logits, seen, cur_tok, finished, out_ids, margins, eos_ids, n_eos, pad_id, B, V, ldl,
                                                  rep_penalty, temperature, top_k, top_p, seed, row_id, step, out_stride, scratch,
-                                                 seen_prev, stream);
+                                                 seen_prev, sx ? &x : nullptr, stream);
         if (rc != O3V_OK) return rc;
     } else {
         const int rc = o3v_sample_greedy_ex(logits, seen, cur_tok, finished, out_ids, margins, eos_ids, n_eos, pad_id, B, V, ldl,
-                                            rep_penalty, step, out_stride, scratch, embed, x_out, hidden, seen_prev, stream);
+                                            rep_penalty, step, out_stride, scratch, embed, x_out, hidden, seen_prev, sx ? &x : nullptr,
+                                            stream);
         if (rc != O3V_OK) return rc;
         temperature = 1.0f;  // the greedy sampler applies the penalty only
     }
-    if (B == 0) return O3V_OK;
+    if (B == 0 || !lp) return O3V_OK;
     const bf16_t* lg = (const bf16_t*)logits;
     const uint8_t* sn = (const uint8_t*)seen;
     const int rs = WS_FLOATS / 2;
     u64* rec = ws + LP_OFF;
-    if (do_sample) {
-        O3V_KLAUNCH(lp_partial_kernel<true>, dim3(NBLK, B), dim3(NT), 0, stream, lg, sn, ws, rec, rs, NBLK, cur_tok, seen_prev, V, ldl,
-                    rep_penalty, temperature, lp->n);
-        O3V_KLAUNCH(lp_final_kernel<true>, dim3(B), dim3(64), 0, stream, lg, ws, rec, rs, NBLK, cur_tok, seen_prev, V, ldl, rep_penalty,
-                    temperature, lp->n, lp->chosen_lp, lp->chosen_rank, lp->top_ids, lp->top_lp, out_stride, step);
+#define LP_ARGS_P lg, sn, ws, rec, rs, NBLK, cur_tok, seen_prev, V, ldl, rep_penalty, temperature, lp->n
+#define LP_ARGS_F \
+    lg, ws, rec, rs, NBLK, cur_tok, seen_prev, V, ldl, rep_penalty, temperature, lp->n, lp->chosen_lp, lp->chosen_rank, lp->top_ids, \
+        lp->top_lp, out_stride, step
+    if (sx && do_sample) {
+        O3V_KLAUNCH(lp_partial_kernel_x<true>, dim3(NBLK, B), dim3(NT), 0, stream, LP_ARGS_P, x);
+        O3V_KLAUNCH(lp_final_kernel_x<true>, dim3(B), dim3(64), 0, stream, LP_ARGS_F, x);
+    } else if (sx) {
+        O3V_KLAUNCH(lp_partial_kernel_x<false>, dim3(NBLK, B), dim3(NT), 0, stream, LP_ARGS_P, x);
+        O3V_KLAUNCH(lp_final_kernel_x<false>, dim3(B), dim3(64), 0, stream, LP_ARGS_F, x);
+    } else if (do_sample) {
+        O3V_KLAUNCH(lp_partial_kernel<true>, dim3(NBLK, B), dim3(NT), 0, stream, LP_ARGS_P);
+        O3V_KLAUNCH(lp_final_kernel<true>, dim3(B), dim3(64), 0, stream, LP_ARGS_F);
     } else {
-        O3V_KLAUNCH(lp_partial_kernel<false>, dim3(NBLK, B), dim3(NT), 0, stream, lg, sn, ws, rec, rs, NBLK, cur_tok, seen_prev, V, ldl,
-                    rep_penalty, temperature, lp->n);
-        O3V_KLAUNCH(lp_final_kernel<false>, dim3(B), dim3(64), 0, stream, lg, ws, rec, rs, NBLK, cur_tok, seen_prev, V, ldl, rep_penalty,
-                    temperature, lp->n, lp->chosen_lp, lp->chosen_rank, lp->top_ids, lp->top_lp, out_stride, step);
+        O3V_KLAUNCH(lp_partial_kernel<false>, dim3(NBLK, B), dim3(NT), 0, stream, LP_ARGS_P);
+        O3V_KLAUNCH(lp_final_kernel<false>, dim3(B), dim3(64), 0, stream, LP_ARGS_F);
     }
+#undef LP_ARGS_P
+#undef LP_ARGS_F
     O3V_CHECK_LAUNCH();
     return O3V_OK;
 }
@@ -769,9 +959,44 @@ extern "C" int o3v_sample_logprobs(const void* logits, void* seen, int* cur_tok,
                                    const int* eos_ids, int n_eos, int pad_id, int B, int V, int ldl, int do_sample, float rep_penalty,
                                    float temperature, int top_k, float top_p, uint64_t seed, const int* row_id, int step,
                                    int out_stride, float* scratch, const o3v_logprob_opts* lp, hipStream_t stream) {
+    if (!lp) return O3V_ERR_ARG;
     return o3v_sample_lp_step(logits, seen, cur_tok, finished, out_ids, margins, eos_ids, n_eos, pad_id, B, V, ldl, do_sample,
                               rep_penalty, temperature, top_k, top_p, seed, row_id, step, out_stride, scratch, nullptr, nullptr, 0, lp,
-                              stream);
+                              nullptr, stream);
+}
+
+// o3v_sampling_opts -> the controls of decode step `step`; O3V_ERR_ARG for what the header rules out (host only, before any launch)
+int o3v_sampling_resolve(const o3v_sampling_opts* so, int step, o3v_samp_x* x) {
+    if (!so || !x || step < 0) return O3V_ERR_ARG;
+    if (!(so->min_p >= 0.f && so->min_p <= 1.f) || !(fabsf(so->presence) <= 2.f) || !(fabsf(so->frequency) <= 2.f) || so->min_tokens < 0)
+        return O3V_ERR_ARG;   // (the negated forms refuse NaN)
+    if ((so->presence != 0.f || so->frequency != 0.f) && !so->out_counts) return O3V_ERR_ARG;
+    if (so->min_tokens > 0 && !so->bias_early) return O3V_ERR_ARG;
+    if ((reinterpret_cast<uintptr_t>(so->bias) & 15) || (reinterpret_cast<uintptr_t>(so->bias_early) & 15) ||
+        (reinterpret_cast<uintptr_t>(so->out_counts) & 15))
+        return O3V_ERR_ARG;
+    x->bias = step < so->min_tokens ? so->bias_early : so->bias;
+    x->counts = so->out_counts;
+    x->cnt_prev = nullptr;
+    x->pres = so->presence;
+    x->freq = so->frequency;
+    unsigned bits;
+    memcpy(&bits, &so->min_p, 4);
+    x->minp_bits = bits;
+    return O3V_OK;
+}
+
+extern "C" int o3v_sample_step_ex(const void* logits, void* seen, int* cur_tok, int* finished, int* out_ids, float* margins,
+                                  const int* eos_ids, int n_eos, int pad_id, int B, int V, int ldl, int do_sample, float rep_penalty,
+                                  float temperature, int top_k, float top_p, uint64_t seed, const int* row_id, int step,
+                                  int out_stride, float* scratch, const o3v_logprob_opts* lp, const o3v_sampling_opts* so,
+                                  hipStream_t stream) {
+    o3v_samp_x x;
+    const int rc = o3v_sampling_resolve(so, step, &x);
+    if (rc != O3V_OK) return rc;
+    return o3v_sample_lp_step(logits, seen, cur_tok, finished, out_ids, margins, eos_ids, n_eos, pad_id, B, V, ldl, do_sample,
+                              rep_penalty, temperature, top_k, top_p, seed, row_id, step, out_stride, scratch, nullptr, nullptr, 0, lp,
+                              &x, stream);
 }
 
 extern "C" int o3v_logprobs_rows(const void* logits, const int* target, int R, int V, int ldl, int n, float* target_lp,

@@ -409,7 +409,9 @@ class O3VEngine:
                  top_k: int = 0, num_return_sequences: int = 1, seed: int = 0, row_ids: Optional[Sequence[int]] = None,
                  vis_embeds: Optional[torch.Tensor] = None, steps_per_sync: int = 16, return_margins: bool = True,
                  sync_timings: bool = False, prefix_key=None, pixel_values_videos=None, video_grid_thw=None, video_frames=None,
-                 second_per_grid_ts=None, logprobs: int = 0, prompt_logprobs: int = 0, _fused_ok: bool = True) -> GenerateOutput:
+                 second_per_grid_ts=None, logprobs: int = 0, prompt_logprobs: int = 0, min_p: float = 0.0,
+                 presence_penalty: float = 0.0, frequency_penalty: float = 0.0, min_new_tokens: int = 0, token_bias=None,
+                 allowed_token_ids=None, banned_token_ids=None, stop_checker=None, _fused_ok: bool = True) -> GenerateOutput:
         """HF-semantics generate.  `num_return_sequences=G` shares ONE ViT pass and ONE prefill across the G
         completions of a prompt (the reference recomputes both G times, TF:1493-1579) and fans the KV cache out.
 
@@ -423,7 +425,16 @@ class O3VEngine:
         was drawn from (GenerateOutput.logprobs; o3v_logprob_opts).  `prompt_logprobs=N`: the same for every prompt token after the
         first on the raw logits, from the prefill's hidden rows in chunks (GenerateOutput.prompt_logprobs).  A call asking for prompt
         log-probs does not reuse (or store) prefix K/V under `prefix_key`: reused rows have no hidden state to score.  With both 0
-        nothing changes: no extra buffer, the same decode calls."""
+        nothing changes: no extra buffer, the same decode calls.
+
+        Sampling controls beyond HF's (vLLM 0.7.2 SamplingParams, o3v_sampling_opts), all decided inside the
+        sampler's own passes: `min_p` (sampling only; greedy ignores it), `presence_penalty` / `frequency_penalty` over the tokens
+        the row has emitted, `token_bias` {id: float} added to the logits, `allowed_token_ids` / `banned_token_ids` as -inf masks,
+        `min_new_tokens`: no id of `eos_token_ids` before that many tokens.  With all of them at their defaults the decode calls
+        and buffers are the plain ones.  `stop_checker(ids)` is called at every chunk boundary (`steps_per_sync` steps) with the
+        int64 CPU tensor [rows, done] of what has been emitted; it returns {row: n} (or (row, n) pairs): row ends after its first n
+        tokens.  Such a row emits pad from the next step on, what it emitted past n is replaced by pad, and the trailing-pad trim
+        counts it as finished at n."""
         cfg, tc = self.cfg, self.cfg.text
         ids = np.asarray(input_ids.cpu() if torch.is_tensor(input_ids) else input_ids, dtype=np.int64)
         if ids.ndim == 1:
@@ -447,6 +458,9 @@ class O3VEngine:
         for what, v in (("logprobs", n_lp), ("prompt_logprobs", n_plp)):
             if not 0 <= v <= _lib.MAX_LOGPROBS:
                 raise ValueError(f"`{what}` must be in 0..{_lib.MAX_LOGPROBS}, got {v}")
+        V_ = tc.vocab_size
+        sampling = self._sampling_vectors(V_, T, eos_token_ids, bool(do_sample), min_p, presence_penalty, frequency_penalty,
+                                          min_new_tokens, token_bias, allowed_token_ids, banned_token_ids)
         tm = {}
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)] if sync_timings else None
 
@@ -557,7 +571,17 @@ class O3VEngine:
                 nsplit = -nsplit
         part_o = torch.empty(n_rep_total * 64 * tc.head_dim, dtype=torch.float32, device=self.dev)
         part_ml = torch.empty(n_rep_total * 64 * 2, dtype=torch.float32, device=self.dev)
-        scratch = torch.empty((B, _lib.SAMPLE_SCRATCH_FLOATS if do_sample or n_lp else 256), dtype=torch.float32, device=self.dev)
+        scratch = torch.empty((B, _lib.SAMPLE_SCRATCH_FLOATS if do_sample or n_lp or sampling else 256), dtype=torch.float32,
+                              device=self.dev)
+        so = so_keep = None
+        if sampling:    # the extended sampler kernels: static-edit vectors and (penalties only) the u16 output counts
+            bias, early = (None if v is None else torch.from_numpy(v).to(self.dev) for v in (sampling["bias"], sampling["bias_early"]))
+            counts = torch.zeros((B, V_), dtype=torch.int16, device=self.dev) if sampling["counts"] else None
+            so_keep = (bias, early, counts)
+            so = _lib.SamplingOpts(min_p=sampling["min_p"], presence=sampling["presence"], frequency=sampling["frequency"],
+                                   min_tokens=sampling["min_tokens"], bias=0 if bias is None else bias.data_ptr(),
+                                   bias_early=0 if early is None else early.data_ptr(),
+                                   out_counts=0 if counts is None else counts.data_ptr())
         lp = lp_opts = None
         if n_lp:
             lp = Logprobs(token=torch.zeros((B, T), dtype=torch.float32, device=self.dev),
@@ -596,7 +620,8 @@ class O3VEngine:
         # ---- decode loop: chunks of steps enqueued from C++, one host check per chunk (TF:utils.py:2936-2937)
         done = 0
         use_eos = len(eos_token_ids) > 0
-        chunk = max(1, int(steps_per_sync)) if use_eos else T
+        chunk = max(1, int(steps_per_sync)) if (use_eos or stop_checker is not None) else T
+        ended = {}      # rows the stop checker ended -> number of tokens they keep
 
         def check_waits():
             if sync is None:
@@ -608,7 +633,10 @@ class O3VEngine:
         while done < T:
             # the first chunk is short whenever the one-launch block is in use: its time-out word is read right after it
             n = min(chunk if (done or sync is None) else min(chunk, getattr(self, "_first_chunk", 16)), T - done)
-            if lp_opts is None:
+            if so is not None:
+                _lib.call("o3v_llm_decode_ex", C.byref(self.w.llm), C.byref(st), None if lp_opts is None else C.byref(lp_opts),
+                          C.byref(so), done, n, int(done + n == T), _stream())
+            elif lp_opts is None:
                 _lib.call("o3v_llm_decode", C.byref(self.w.llm), C.byref(st), done, n, int(done + n == T), _stream())
             else:
                 _lib.call("o3v_llm_decode_lp", C.byref(self.w.llm), C.byref(st), C.byref(lp_opts), done, n, int(done + n == T), _stream())
@@ -616,7 +644,17 @@ class O3VEngine:
             done += n
             if first and done < T:
                 check_waits()
-            if use_eos and done < T and bool(finished.all().item()):
+            if stop_checker is not None:
+                hits = stop_checker(out_ids[:, :done].to(torch.int64).cpu())
+                for b, end in (hits.items() if hasattr(hits, "items") else (hits or ())):
+                    b, end = int(b), int(end)
+                    if not (0 <= b < B and 0 <= end <= done):
+                        raise ValueError(f"stop_checker: row {b} / end {end} outside [0, {B}) x [0, {done}]")
+                    if b not in ended:
+                        ended[b] = end
+                        finished[b] = 1
+                        out_ids[b, end:] = pad_id
+            if (use_eos or ended) and done < T and bool(finished.all().item()):
                 break
         mark(3)
         layers_run = stats[0] * tc.num_hidden_layers
@@ -628,11 +666,23 @@ class O3VEngine:
             self._debug_last = {"kc": kc, "vc": vc, "logits": logits, "x": xdec, "S": S, "cos": cosd, "sin": sind, "k_lo": k_lo,
                                 "nsplit": nsplit, "Tmax": Tmax, "out_ids": out_ids}
         gen = out_ids[:, :done].to(torch.int64)
-        if use_eos and done > 0:
+        if use_eos and done > 0 and not ended:
             # HF stops at the step where every row has finished: trim trailing all-pad columns generated past it
             fin_col = self._first_all_finished(gen, eos_token_ids, pad_id)
             gen = gen[:, :fin_col]
             done = fin_col
+        elif ended and done > 0:
+            # the same, a row the stop checker ended finishing at the column the checker named (or at its EOS if that came first)
+            g = gen.cpu().numpy()
+            fin_at = np.full(B, done, dtype=np.int64)
+            for b in range(B):
+                hit = np.flatnonzero(np.isin(g[b], list(eos_token_ids))) if use_eos else np.empty(0, dtype=np.int64)
+                if hit.size:
+                    fin_at[b] = hit[0] + 1
+                if b in ended:
+                    fin_at[b] = min(fin_at[b], ended[b])
+            done = int(max(1, min(done, fin_at.max())))
+            gen = gen[:, :done]
         prompt = torch.from_numpy(ids_rep).to(self.dev)
         seqs = torch.cat([prompt, gen], dim=1)
         if ev is not None:
@@ -643,6 +693,63 @@ class O3VEngine:
             lp = Logprobs(lp.token[:, :done], lp.rank[:, :done], lp.top_ids[:, :done], lp.top[:, :done])
         return GenerateOutput(sequences=seqs, margins=None if margins is None else margins[:, :done], n_steps=done,
                               timings=tm, logprobs=lp, prompt_logprobs=plp)
+
+    @staticmethod
+    def _sampling_vectors(V: int, T: int, eos_token_ids, do_sample: bool, min_p, presence_penalty, frequency_penalty,
+                          min_new_tokens, token_bias, allowed_token_ids, banned_token_ids):
+        """Host side of o3v_sampling_opts: None when every control is at its default (the plain decode calls then), else the
+        scalars and the two dense f32 [V] vectors of static edits -- `bias` (token_bias, -inf outside the allowed set and at banned
+        ids; None when there is no edit) and `bias_early` (the same with every EOS id at -inf, for the steps before
+        min_new_tokens).  Pure numpy: no GPU needed."""
+        min_p, pres, freq, min_new = float(min_p or 0.0), float(presence_penalty or 0.0), float(frequency_penalty or 0.0), \
+            int(min_new_tokens or 0)
+        if not 0.0 <= min_p <= 1.0:
+            raise ValueError(f"`min_p` must be in [0, 1], got {min_p}")
+        for what, v in (("presence_penalty", pres), ("frequency_penalty", freq)):
+            if not -2.0 <= v <= 2.0:
+                raise ValueError(f"`{what}` must be in [-2, 2], got {v}")
+        if min_new < 0:
+            raise ValueError(f"`min_new_tokens` must be >= 0, got {min_new}")
+        if not do_sample:
+            min_p = 0.0      # greedy ignores top_k / top_p / min_p
+        eos = [int(e) for e in eos_token_ids]
+        if not eos or min_new == 0:
+            min_new = 0      # nothing to hold back
+        static = bool(token_bias) or allowed_token_ids is not None or bool(banned_token_ids is not None and len(banned_token_ids))
+        if not (min_p or pres or freq or min_new or static):
+            return None
+        bias = None
+        if static:
+            bias = np.zeros(V, dtype=np.float32)
+            for t, v in dict(token_bias or {}).items():
+                if not 0 <= int(t) < V or not np.isfinite(float(v)):
+                    raise ValueError(f"token_bias: token id {t} outside the vocabulary or bias {v} not finite")
+                bias[int(t)] += np.float32(v)
+            if allowed_token_ids is not None:
+                allowed = np.asarray(list(allowed_token_ids), dtype=np.int64).reshape(-1)
+                if allowed.size == 0 or allowed.min() < 0 or allowed.max() >= V:
+                    raise ValueError("allowed_token_ids must be a non-empty list of ids inside the vocabulary")
+                outside = np.ones(V, dtype=bool)
+                outside[allowed] = False
+                bias[outside] = -np.inf
+            if banned_token_ids is not None and len(banned_token_ids):
+                banned = np.asarray(list(banned_token_ids), dtype=np.int64).reshape(-1)
+                if banned.min() < 0 or banned.max() >= V:
+                    raise ValueError("banned_token_ids must lie inside the vocabulary")
+                bias[banned] = -np.inf
+            if not np.isfinite(bias).any():
+                raise ValueError("allowed_token_ids minus the banned tokens is empty: no token could be emitted")
+        early = None
+        if min_new:
+            early = np.zeros(V, dtype=np.float32) if bias is None else bias.copy()
+            early[[e for e in eos if 0 <= e < V]] = -np.inf
+            if not np.isfinite(early).any():
+                raise ValueError("every allowed token is a stop id while min_new_tokens > 0: no token could be emitted")
+        counts = bool(pres or freq)
+        if counts and T > _lib.MAX_COUNT:
+            raise ValueError(f"presence / frequency penalties count emitted tokens in 16 bits: max_new_tokens <= {_lib.MAX_COUNT}")
+        return {"min_p": min_p, "presence": pres, "frequency": freq, "min_tokens": min_new, "bias": bias, "bias_early": early,
+                "counts": counts}
 
     def _prompt_logprobs(self, xs: torch.Tensor, ids: np.ndarray, n: int, rows_per_chunk: int = 2048) -> Logprobs:
         """Prompt log-probs from the prefill's hidden rows xs [B0, S, H]: row j of prompt b predicts ids[b, j+1].  The head runs on

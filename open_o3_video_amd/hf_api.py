@@ -32,7 +32,8 @@ class IncompatibleKeys(NamedTuple):
 
 class GenerationConfigLike(SimpleNamespace):
     """Duck-typed subset of transformers.GenerationConfig (max_new_tokens, do_sample, temperature, top_k, top_p,
-    repetition_penalty, num_return_sequences, pad_token_id, eos_token_id).  A field that is absent or None is "not set by the
+    repetition_penalty, num_return_sequences, pad_token_id, eos_token_id, and the optional min_p, min_new_tokens,
+    suppress_tokens, bad_words_ids).  A field that is absent or None is "not set by the
     caller", exactly as in transformers >= 5 where GenerationConfig() leaves everything it was not given at None."""
 
 
@@ -40,6 +41,9 @@ class GenerationConfigLike(SimpleNamespace):
 GLOBAL_GENERATION_DEFAULTS = dict(max_new_tokens=20, do_sample=False, temperature=1.0, top_k=50, top_p=1.0,
                                   repetition_penalty=1.0, num_return_sequences=1)
 _GEN_FIELDS = tuple(GLOBAL_GENERATION_DEFAULTS) + ("pad_token_id", "eos_token_id", "bos_token_id")
+# optional logits processors (TF:generation/utils.py _get_logits_processor; None = off): read from the generate() kwargs, then the
+# passed config, then the model's; they reach the engine only when set
+_EXTRA_GEN_FIELDS = ("min_p", "min_new_tokens", "suppress_tokens", "bad_words_ids")
 
 
 def load_generation_config(path: str) -> dict:
@@ -198,6 +202,7 @@ class Qwen2_5_VLForConditionalGeneration:
         common = dict(max_new_tokens=T, eos_token_ids=eos, pad_token_id=pad, repetition_penalty=float(r["repetition_penalty"]),
                       do_sample=do_sample, temperature=float(r["temperature"] or 1.0), top_p=float(r["top_p"] or 1.0),
                       top_k=top_k, seed=self._seed)
+        common.update(self._extra_controls(generation_config, kw, do_sample))
         self._seed += 1
         B = ids.shape[0]
         mask = None if attention_mask is None else torch.as_tensor(attention_mask).cpu().numpy()
@@ -219,6 +224,37 @@ class Qwen2_5_VLForConditionalGeneration:
         L = max(r.shape[1] for r in rows)
         rows = [torch.nn.functional.pad(r, (0, L - r.shape[1]), value=pad) for r in rows]
         return torch.cat(rows, dim=0)
+
+    def _extra_controls(self, generation_config, kw, do_sample: bool) -> dict:
+        """min_p (MinPLogitsWarper, sampling only), min_new_tokens (MinNewTokensLengthLogitsProcessor), suppress_tokens
+        (SuppressTokensLogitsProcessor) and single-token bad_words_ids (NoBadWordsLogitsProcessor) as engine arguments.  Their -inf
+        masks commute with the penalties and the warpers, so the engine's order (masks first) gives what transformers' order gives."""
+        vals = {}
+        for k in _EXTRA_GEN_FIELDS:
+            v = kw.get(k)
+            for src in (generation_config, self.generation_config):
+                if v is None and src is not None:
+                    v = getattr(src, k, None)
+            vals[k] = v
+        out = {}
+        if vals["min_p"] is not None and do_sample:
+            if not 0.0 <= float(vals["min_p"]) <= 1.0:
+                raise ValueError(f"`min_p` has to be a float in the [0, 1] interval, but is {vals['min_p']}")
+            if float(vals["min_p"]) > 0:
+                out["min_p"] = float(vals["min_p"])
+        if vals["min_new_tokens"]:
+            if int(vals["min_new_tokens"]) < 0:
+                raise ValueError(f"`min_new_tokens` has to be a positive integer, but is {vals['min_new_tokens']}")
+            out["min_new_tokens"] = int(vals["min_new_tokens"])
+        banned = [int(t) for t in (vals["suppress_tokens"] or ())]
+        for w in vals["bad_words_ids"] or ():
+            w = [int(t) for t in w]
+            if len(w) != 1:
+                raise NotImplementedError(f"bad_words_ids: only single-token entries are supported, got {w}")
+            banned += w
+        if banned:
+            out["banned_token_ids"] = list(dict.fromkeys(banned))
+        return out
 
     def _route_video(self, ids, pixel_values, image_grid_thw, pixel_values_videos, video_grid_thw):
         """Video tensors behind <|video_pad|> placeholders run the native video path.  Video tensors whose prompt marks the frames

@@ -45,12 +45,103 @@ class SamplingParams:
     seed: Optional[int] = None
     logprobs: Optional[int] = None          # per output token: its log-prob + the N most likely (0: the token's only)
     prompt_logprobs: Optional[int] = None   # the same for every prompt token after the first
+    # the rest of vLLM 0.7.2's sampling controls (defaults and checks of SamplingParams._verify_args; semantics: INTEGRATION.md a14)
+    top_k: int = -1                         # -1: off
+    min_p: float = 0.0
+    presence_penalty: float = 0.0
+    frequency_penalty: float = 0.0
+    min_tokens: int = 0
+    stop: Any = None                        # str or list of str
+    include_stop_str_in_output: bool = False
+    ignore_eos: bool = False
+    skip_special_tokens: bool = True
+    logit_bias: Optional[dict] = None       # {token id: bias}
+    allowed_token_ids: Optional[Sequence[int]] = None
+    bad_words: Optional[Sequence[str]] = None
+    # vLLM arguments that are not built: anything but None is refused by name
+    best_of: Any = None
+    logits_processors: Any = None
+    guided_decoding: Any = None
+    truncate_prompt_tokens: Any = None
 
     def __post_init__(self):
         for name in ("logprobs", "prompt_logprobs"):
             v = getattr(self, name)
             if v is not None and not 0 <= int(v) <= MAX_LOGPROBS:
                 raise ValueError(f"Requested {name} of {v}, which is outside the allowed range 0..{MAX_LOGPROBS}")
+        for name in ("best_of", "logits_processors", "guided_decoding", "truncate_prompt_tokens"):
+            if getattr(self, name) is not None:
+                raise ValueError(f"SamplingParams.{name} is not supported")
+        if isinstance(self.seed, (list, tuple)):
+            raise ValueError("SamplingParams.seed: a per-request list of seeds is not supported (pass a list of SamplingParams)")
+        if isinstance(self.top_k, bool) or int(self.top_k) != self.top_k or self.top_k < -1 or self.top_k == 0:
+            raise ValueError(f"top_k must be -1 (disable), or at least 1, got {self.top_k}.")
+        self.top_k = int(self.top_k)
+        if not 0.0 <= self.min_p <= 1.0:
+            raise ValueError(f"min_p must be in [0, 1], got {self.min_p}.")
+        for name in ("presence_penalty", "frequency_penalty"):
+            if not -2.0 <= getattr(self, name) <= 2.0:
+                raise ValueError(f"{name} must be in [-2, 2], got {getattr(self, name)}.")
+        if int(self.min_tokens) != self.min_tokens or self.min_tokens < 0:
+            raise ValueError(f"min_tokens must be greater than or equal to 0, got {self.min_tokens}.")
+        if self.max_tokens is not None and self.min_tokens > self.max_tokens:
+            raise ValueError(f"min_tokens must be less than or equal to max_tokens={self.max_tokens}, got {self.min_tokens}.")
+        if self.stop is None:
+            self.stop = []
+        elif isinstance(self.stop, str):
+            self.stop = [self.stop]
+        else:
+            self.stop = list(self.stop)
+        if any(not isinstance(t, str) or not t for t in self.stop):
+            raise ValueError("stop cannot contain an empty string.")
+        if self.logit_bias is not None:
+            try:
+                self.logit_bias = {int(k): float(v) for k, v in dict(self.logit_bias).items()}
+            except (TypeError, ValueError) as e:
+                raise ValueError(f"logit_bias must map token ids to floats: {e}") from None
+            if any(k < 0 or not np.isfinite(v) for k, v in self.logit_bias.items()):
+                raise ValueError("logit_bias: token ids must be >= 0 and biases finite")
+        if self.allowed_token_ids is not None:
+            self.allowed_token_ids = [int(t) for t in self.allowed_token_ids]
+            if not self.allowed_token_ids or min(self.allowed_token_ids) < 0:
+                raise ValueError("allowed_token_ids must be a non-empty list of token ids")
+        if self.bad_words is not None:
+            self.bad_words = list(self.bad_words)
+            if any(not isinstance(w, str) or not w for w in self.bad_words):
+                raise ValueError("bad_words cannot contain an empty string.")
+
+
+class _IncrementalDetokenizer:
+    """Text of a growing token list, one token at a time (the prefix / read offset scheme of vLLM's detokenize_incrementally and
+    HF's TextStreamer: a token's text is what decoding adds behind the text of the tokens before it, held back while it ends in an
+    incomplete UTF-8 sequence).  `ends[j]` = len(text) after token j."""
+
+    def __init__(self, decode):
+        self.decode, self.toks, self.text, self.ends, self.prefix, self.read = decode, [], "", [], 0, 0
+
+    def push(self, tok: int):
+        self.toks.append(int(tok))
+        before = self.decode(self.toks[self.prefix:self.read]) if self.read > self.prefix else ""
+        now = self.decode(self.toks[self.prefix:])
+        if len(now) > len(before) and not now.endswith("\ufffd"):
+            self.text += now[len(before):]
+            self.prefix, self.read = self.read, len(self.toks)
+        self.ends.append(len(self.text))
+
+
+def find_stop(detok: "_IncrementalDetokenizer", j: int, stop: Sequence[str]):
+    """vLLM's StopChecker for stop strings at token j (0-based) of `detok`: the first string of `stop` that the token's text
+    completes (an occurrence that ends inside the characters this token added) -> (string, index of its first character)."""
+    old = detok.ends[j - 1] if j else 0
+    new = detok.ends[j]
+    if new == old:
+        return None
+    text = detok.text[:new]
+    for s_ in stop:
+        i = text.find(s_, max(0, old - len(s_) + 1))
+        if i >= 0:
+            return s_, i
+    return None
 
 
 @dataclass
@@ -68,6 +159,7 @@ class CompletionOutput:
     finish_reason: str = "length"
     cumulative_logprob: Optional[float] = None
     logprobs: Optional[List[dict]] = None    # one {token_id: Logprob} per token of token_ids
+    stop_reason: Any = None                  # None: EOS or length; the token id of a stop_token_ids hit; the string of a stop hit
 
 
 @dataclass
@@ -338,18 +430,124 @@ class LLM:
         ids = self.tokenizer.encode(prompt, add_special_tokens=False) if hasattr(self.tokenizer, "encode") else self.tokenizer(prompt)
         return list(ids)
 
-    def generate(self, inputs, sampling_params: Optional[SamplingParams] = None, use_tqdm: bool = False):
-        sp = sampling_params or SamplingParams()
+    def _banned_ids(self, sp: SamplingParams) -> List[int]:
+        """bad_words as vLLM tokenises them (the word, and the word behind a space): single-token results are banned outright,
+        anything longer would need per-step host logic and is refused."""
+        banned = []
+        for w in sp.bad_words or ():
+            for text in (w.lstrip(), " " + w.lstrip()):
+                ids = list(self.tokenizer.encode(text, add_special_tokens=False))
+                if len(ids) > 1:
+                    raise ValueError(f"bad_words: {w!r} tokenises to {len(ids)} tokens; only single-token bad words are supported")
+                banned += [int(t) for t in ids if int(t) not in banned]
+        return banned
+
+    def generate(self, inputs, sampling_params=None, use_tqdm: bool = False):
+        """`sampling_params`: one SamplingParams for every request, or a list with one per request.  Requests with equal parameters
+        run together exactly as a single-parameter call runs them; results come back in input order, and request ids / default
+        seeds follow the input position, so a request's samples do not depend on what it was grouped with."""
         if isinstance(inputs, dict):
             inputs = [inputs]
+        inputs = list(inputs)
+        if not isinstance(sampling_params, (list, tuple)):
+            return self._generate_group(inputs, sampling_params or SamplingParams(), list(range(len(inputs))))
+        if len(sampling_params) != len(inputs):
+            raise ValueError(f"The lengths of prompts ({len(inputs)}) and sampling_params ({len(sampling_params)}) must be the same.")
+        groups = []     # (SamplingParams, positions) in order of first appearance
+        for pos, sp in enumerate(sampling_params):
+            sp = sp or SamplingParams()
+            for g in groups:
+                if g[0] == sp:
+                    g[1].append(pos)
+                    break
+            else:
+                groups.append((sp, [pos]))
+        base, results = self._req, [None] * len(inputs)
+        for sp, positions in groups:
+            self._req = base
+            for pos, ro in zip(positions, self._generate_group([inputs[p] for p in positions], sp, positions)):
+                results[pos] = ro
+        self._req = base + len(inputs)
+        return results
+
+    def _generate_group(self, inputs, sp: SamplingParams, positions: Sequence[int]):
+        """The requests `inputs` (input positions `positions` of the generate call) under one SamplingParams."""
+        base = self._req
         greedy = sp.temperature == 0.0
         # vLLM stops on the request's stop ids, the model's eos id and every eos id of the checkpoint's generation_config.json
         stop = list(sp.stop_token_ids) if sp.stop_token_ids else []
-        eos = stop + [e for e in ([self.cfg.eos_token_id] + list(self.generation_eos_ids)) if e is not None and e not in stop]
+        model_eos = [] if sp.ignore_eos else [self.cfg.eos_token_id] + list(self.generation_eos_ids)   # ignore_eos: only the request's own stops
+        eos = stop + [e for e in model_eos if e is not None and e not in stop]
         eos = list(dict.fromkeys(int(e) for e in eos))
         common = dict(max_new_tokens=sp.max_tokens, eos_token_ids=eos, pad_token_id=self.cfg.pad_token_id,
                       repetition_penalty=sp.repetition_penalty, do_sample=not greedy,
                       temperature=1.0 if greedy else sp.temperature, top_p=1.0 if greedy else sp.top_p, return_margins=False)
+        # the newer controls reach the engine only when they differ from their defaults; greedy ignores top_k / top_p / min_p
+        V = self.cfg.text.vocab_size
+        if not greedy and sp.top_k > 0:
+            common["top_k"] = sp.top_k
+        if not greedy and sp.min_p > 0:
+            common["min_p"] = sp.min_p
+        if sp.presence_penalty:
+            common["presence_penalty"] = sp.presence_penalty
+        if sp.frequency_penalty:
+            common["frequency_penalty"] = sp.frequency_penalty
+        if sp.min_tokens > 0:
+            common["min_new_tokens"] = sp.min_tokens
+        if sp.logit_bias:
+            if max(sp.logit_bias) >= V:
+                raise ValueError(f"logit_bias: token id {max(sp.logit_bias)} is outside the vocabulary ({V})")
+            common["token_bias"] = dict(sp.logit_bias)
+        banned = self._banned_ids(sp)
+        if banned:
+            common["banned_token_ids"] = banned
+        if sp.allowed_token_ids is not None:
+            if max(sp.allowed_token_ids) >= V:
+                raise ValueError(f"allowed_token_ids: token id {max(sp.allowed_token_ids)} is outside the vocabulary ({V})")
+            left = set(sp.allowed_token_ids) - set(banned)
+            if not left or (sp.min_tokens > 0 and not left - set(eos)):
+                raise ValueError("allowed_token_ids leaves no token to emit once the banned tokens"
+                                 + (" and, before min_tokens, the stop ids" if left else "") + " are taken out")
+            common["allowed_token_ids"] = list(sp.allowed_token_ids)
+        stop_strs = list(sp.stop)
+
+        def tok_decode(toks):
+            return self.tokenizer.decode(toks, skip_special_tokens=sp.skip_special_tokens)
+
+        def row_end(detok, toks):
+            """Where vLLM's StopChecker ends a row, checked after every single token: (number of tokens kept, finish_reason,
+            stop_reason, text or None).  `detok` holds the text of toks[:len(detok.toks)] and is extended as far as needed."""
+            for j, t in enumerate(toks):
+                if stop_strs and j >= len(detok.toks):
+                    detok.push(t)
+                if j + 1 < sp.min_tokens:
+                    continue        # nothing stops a row before min_tokens
+                if t in eos:        # the stop token is dropped from token_ids and from the text
+                    text = detok.text[:detok.ends[j - 1] if j else 0] if stop_strs else None
+                    return j, "stop", (t if t in stop else None), text
+                hit = find_stop(detok, j, stop_strs) if stop_strs else None
+                if hit is not None:
+                    cut = hit[1] + (len(hit[0]) if sp.include_stop_str_in_output else 0)
+                    return j + 1, "stop", hit[0], detok.text[:cut]
+            return len(toks), "length", None, (detok.text[:detok.ends[len(toks) - 1] if toks else 0] if stop_strs else None)
+
+        def make_checker(n_rows):
+            """engine.generate's stop_checker for one call: rows that a stop string has ended, at the token that completed it."""
+            if not stop_strs:
+                return None, None
+            detoks = [_IncrementalDetokenizer(tok_decode) for _ in range(n_rows)]
+
+            def checker(ids):
+                rows = ids.tolist()
+                if rows and len(rows[0]) < len(detoks[0].toks):     # the engine re-ran the call from step 0
+                    detoks[:] = [_IncrementalDetokenizer(tok_decode) for _ in range(n_rows)]
+                out = {}
+                for b, toks in enumerate(rows):
+                    n, _, stop_reason, _ = row_end(detoks[b], toks)
+                    if isinstance(stop_reason, str):    # (a row that hit a stop id has ended on the GPU already)
+                        out[b] = n
+                return out
+            return checker, detoks
         # logprobs=0 still reports the token's own log-prob: the engine is asked for at least one top entry (0 there means off)
         n_lp = None if sp.logprobs is None else int(sp.logprobs)
         n_plp = None if sp.prompt_logprobs is None else int(sp.prompt_logprobs)
@@ -402,12 +600,11 @@ class LLM:
 
         def finish(ro, index, row, n_prompt, lp=None, i=0):
             toks = row[n_prompt:].tolist()
-            reason = "length"
-            for j, t in enumerate(toks):
-                if t in eos:
-                    toks, reason = toks[:j], "stop"   # vLLM drops the stop token from the text
-                    break
-            co = CompletionOutput(index, self.tokenizer.decode(toks, skip_special_tokens=True), toks, reason)
+            n, reason, stop_reason, text = row_end(_IncrementalDetokenizer(tok_decode), toks)
+            toks = toks[:n]
+            if text is None:
+                text = tok_decode(toks)
+            co = CompletionOutput(index, text, toks, reason, stop_reason=stop_reason)
             if lp is not None:      # trimmed exactly as token_ids
                 tok_lp, rank, top_ids, top_lp = (a[i] for a in lp)
                 co.logprobs = logprob_dicts(toks, tok_lp, rank, top_ids, top_lp, n_lp, decode_one)
@@ -433,32 +630,37 @@ class LLM:
                 grid_parts = [p[3] for p in chunk if p[3] is not None]
                 vgrid_parts = [p[6] for p in chunk if p[6] is not None]
                 spg_all = [x for p in chunk if p[7] for x in p[7]]
+                if stop_strs:
+                    common["stop_checker"] = make_checker(len(chunk))[0]
                 out = self.engine.generate(rows, mask, vis_embeds=cat_visual([p[2] for p in chunk], [v for p in chunk for v in p[5]]),
                                            image_grid_thw=np.concatenate(grid_parts) if grid_parts else None,
                                            video_grid_thw=np.concatenate(vgrid_parts) if vgrid_parts else None,
                                            second_per_grid_ts=spg_all or None,
-                                           row_ids=[self._req + i for i in range(len(chunk))],
+                                           row_ids=[base + positions[c0 + i] for i in range(len(chunk))],
                                            seed=0 if sp.seed is None else sp.seed,
                                            prompt_logprobs=0 if n_plp is None else max(1, n_plp), **common)
                 lp, plp = _host_logprobs(out.logprobs), _host_logprobs(out.prompt_logprobs)
                 for i, p in enumerate(chunk):
-                    ro = RequestOutput(request_id=str(self._req), prompt=p[0], prompt_token_ids=p[1])
+                    ro = RequestOutput(request_id=str(base + positions[c0 + i]), prompt=p[0], prompt_token_ids=p[1])
                     finish(ro, 0, out.sequences[i], L, lp, i)
                     if plp is not None:     # left padding: the row's first real token sits at column L - len(ids)
                         ro.prompt_logprobs = prompt_dicts(plp, i, p[1], L - len(p[1]))
                     results.append(ro)
                     self._req += 1
             return results
-        for prompt, ids, vis_i, grid, vkey, vis_v, vgrid, spg in prepared:
+        for pos, (prompt, ids, vis_i, grid, vkey, vis_v, vgrid, spg) in zip(positions, prepared):
             vis = cat_visual([vis_i], vis_v)
-            ro = RequestOutput(request_id=str(self._req), prompt=prompt, prompt_token_ids=ids)
+            req = base + pos
+            ro = RequestOutput(request_id=str(req), prompt=prompt, prompt_token_ids=ids)
             # n samples of one prompt (self-consistency, R:eval/tts.py:47-123) run in groups of <= 16 decode rows; sample i is
             # keyed by (seed, i) whatever group it lands in, and groups after the first reuse the whole prompt K/V
             for i0 in range(0, sp.n, O3VEngine.MAX_ROWS):
                 g = min(O3VEngine.MAX_ROWS, sp.n - i0)
+                if stop_strs:
+                    common["stop_checker"] = make_checker(g)[0]
                 out = self.engine.generate([ids], None, vis_embeds=vis, image_grid_thw=grid, video_grid_thw=vgrid,
                                            second_per_grid_ts=spg, num_return_sequences=g,
-                                           row_ids=list(range(i0, i0 + g)), seed=self._req if sp.seed is None else sp.seed,
+                                           row_ids=list(range(i0, i0 + g)), seed=req if sp.seed is None else sp.seed,
                                            prefix_key=vkey if self.enable_prefix_caching else None,
                                            prompt_logprobs=0 if n_plp is None or i0 else max(1, n_plp), **common)
                 self.prefix_tokens_reused += int(out.timings.get("prefix_tokens_reused", 0))
