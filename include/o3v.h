@@ -543,10 +543,16 @@ typedef struct {
     /* optional HOST array of 4 counters the call adds to: decode forwards, kernel launches inside their layer loops, layers whose
      * attention half ran as the one-launch block, layers whose attention half ran on the stand-alone kernels */
     long long* host_stats;
-    /* bit 0: batch-1 bf16 decode may use the persistent layer block (o3v_decode_layer_block) where its shapes allow, then one
-     * launch for the attention half + gate/up and one for down_proj per layer; otherwise o3v_decode_attn_block + two launches */
-    int flags;
+    int flags;                   /* O3V_DECODE_* below, or'ed */
 } o3v_decode_state;
+/* o3v_decode_state.flags.  LAYER_BLOCK: batch-1 bf16 decode may use the persistent layer block (o3v_decode_layer_block) where its
+ * shapes allow, then one launch for the attention half + gate/up and one for down_proj per layer; otherwise o3v_decode_attn_block +
+ * two launches.  NO_TAIL_NORM (inverted: set = off): at 8..32 bf16 rows with `sync` given, o_proj / down_proj do NOT normalise their
+ * result for the linear that follows (o3v_linear_decode_norm_next); the norms are launches of their own.  NO_QKV_FUSED_NORM (inverted
+ * as well): at 8 rows q/k/v does NOT take its RMSNorm fused; the norm is a launch of its own as at 9..32 rows. */
+#define O3V_DECODE_LAYER_BLOCK 1
+#define O3V_DECODE_NO_TAIL_NORM 2
+#define O3V_DECODE_NO_QKV_FUSED_NORM 4
 
 /* GenerationMixin._sample loop, TF:generation/utils.py:2783-2942, steps [step0, step0+n_steps): sample from
  * st->logits, then (unless it is the globally last step) run one decode forward to refill st->logits. */

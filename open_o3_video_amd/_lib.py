@@ -180,6 +180,8 @@ SAMPLE_SCRATCH_FLOATS = 40960   # O3V_SAMPLE_SCRATCH_FLOATS in include/o3v.h
 MAX_LOGPROBS = 20               # O3V_MAX_LOGPROBS
 MAX_COUNT = 65535               # the u16 output counts of o3v_sampling_opts saturate here
 LOGPROB_ROW_SCRATCH_FLOATS = 384  # O3V_LOGPROB_ROW_SCRATCH_FLOATS
+# o3v_decode_state.flags: O3V_DECODE_LAYER_BLOCK, O3V_DECODE_NO_TAIL_NORM, O3V_DECODE_NO_QKV_FUSED_NORM (the last two switch a form OFF)
+DECODE_LAYER_BLOCK, DECODE_NO_TAIL_NORM, DECODE_NO_QKV_FUSED_NORM = 1, 2, 4
 
 _lib = None
 

@@ -363,26 +363,10 @@ extern "C" int o3v_llm_prefill_ex(const o3v_llm_desc* d, void* x, const void* co
         if (w8a8) {
             TRY(o3v_rmsnorm_quantize_fp8(x, lw.ln1, w.a8, w.sa, rows, H, H, H, d->rms_eps, s));
             TRY(o3v_gemm_fp8(w.a8, w.sa, lw.qkv_w8, lw.qkv_s, lw.qkv_b, nullptr, w.qkv, rows, NQKV, H, H, H, NQKV, 0, O3V_EPI_NONE, s));
-            if (lw.q_norm)
-                TRY(o3v_qkv_norm_rope_cache(w.qkv, lw.q_norm, lw.k_norm, d->rms_eps, cosT, sinT, w.q, kc, vc, own_past, rows, S, Hq, Hkv, D,
-                                            Tmax, S, 0, s));
-            else
-                TRY(o3v_qkv_rope_cache(w.qkv, cosT, sinT, w.q, kc, vc, own_past, rows, S, Hq, Hkv, D, Tmax, S, 0, s));
-            TRY(o3v_attn_tiles_prefix(w.q, kc, vc, kp, vp, p_hs, p_bs, o.prefix_len, pfx ? o.rows_per_prefix : 1, w.att, tiles, n_tiles,
-                                      rows_per_tile, Hq, Hq / Hkv, D, QD, D, (long)Tmax * D, (long)Hkv * Tmax * D, D, (long)Tmax * D,
-                                      (long)Hkv * Tmax * D, QD, scale, s));
-            TRY(o3v_quantize_rows_fp8(w.att, w.a8, w.sa, rows, QD, QD, QD, s));
-            TRY(o3v_gemm_fp8(w.a8, w.sa, lw.o_w8, lw.o_s, nullptr, x, x, rows, H, QD, QD, QD, H, H, O3V_EPI_RESIDUAL, s));
-            TRY(o3v_rmsnorm_quantize_fp8(x, lw.ln2, w.a8, w.sa, rows, H, H, H, d->rms_eps, s));
-            TRY(o3v_gemm_fp8(w.a8, w.sa, lw.gu_w8, lw.gu_s, nullptr, nullptr, w.mlp, rows, 2 * I, H, H, H, I, 0, O3V_EPI_SWIGLU, s));
-            TRY(o3v_quantize_rows_fp8(w.mlp, w.m8, w.sa, rows, I, I, I, s));
-            TRY(o3v_gemm_fp8(w.m8, w.sa, lw.down_w8, lw.down_s, nullptr, x, x, rows, H, I, I, I, H, H, O3V_EPI_RESIDUAL, s));
-            if (l < n_deep && n_ds > 0)
-                TRY(o3v_add_rows(x, o.ds_rows, o.ds_src, (const char*)o.ds_feat + (size_t)l * o.ds_stride * 2, n_ds, H, s));
-            continue;
+        } else {
+            TRY(o3v_rmsnorm(x, lw.ln1, w.h, rows, H, H, H, d->rms_eps, s));
+            TRY(linear(w.h, lw.qkv_w, lw.qkv_b, nullptr, w.qkv, rows, NQKV, H, H, NQKV, 0, O3V_EPI_NONE, s, w.splitk, w.splitk_bytes, d->gemm_tile));
         }
-        TRY(o3v_rmsnorm(x, lw.ln1, w.h, rows, H, H, H, d->rms_eps, s));
-        TRY(linear(w.h, lw.qkv_w, lw.qkv_b, nullptr, w.qkv, rows, NQKV, H, H, NQKV, 0, O3V_EPI_NONE, s, w.splitk, w.splitk_bytes, d->gemm_tile));
         if (lw.q_norm)
             TRY(o3v_qkv_norm_rope_cache(w.qkv, lw.q_norm, lw.k_norm, d->rms_eps, cosT, sinT, w.q, kc, vc, own_past, rows, S, Hq, Hkv, D,
                                         Tmax, S, 0, s));
@@ -391,10 +375,19 @@ extern "C" int o3v_llm_prefill_ex(const o3v_llm_desc* d, void* x, const void* co
         TRY(o3v_attn_tiles_prefix(w.q, kc, vc, kp, vp, p_hs, p_bs, o.prefix_len, pfx ? o.rows_per_prefix : 1, w.att, tiles, n_tiles,
                                   rows_per_tile, Hq, Hq / Hkv, D, QD, D, (long)Tmax * D, (long)Hkv * Tmax * D, D, (long)Tmax * D,
                                   (long)Hkv * Tmax * D, QD, scale, s));
-        TRY(linear(w.att, lw.o_w, nullptr, x, x, rows, H, QD, QD, H, H, O3V_EPI_RESIDUAL, s, w.splitk, w.splitk_bytes, d->gemm_tile));
-        TRY(o3v_rmsnorm(x, lw.ln2, w.h, rows, H, H, H, d->rms_eps, s));
-        TRY(linear(w.h, lw.gu_w, nullptr, nullptr, w.mlp, rows, 2 * I, H, H, I, 0, O3V_EPI_SWIGLU, s, nullptr, 0, d->gemm_tile));
-        TRY(linear(w.mlp, lw.down_w, nullptr, x, x, rows, H, I, I, H, H, O3V_EPI_RESIDUAL, s, w.splitk, w.splitk_bytes, d->gemm_tile));
+        if (w8a8) {
+            TRY(o3v_quantize_rows_fp8(w.att, w.a8, w.sa, rows, QD, QD, QD, s));
+            TRY(o3v_gemm_fp8(w.a8, w.sa, lw.o_w8, lw.o_s, nullptr, x, x, rows, H, QD, QD, QD, H, H, O3V_EPI_RESIDUAL, s));
+            TRY(o3v_rmsnorm_quantize_fp8(x, lw.ln2, w.a8, w.sa, rows, H, H, H, d->rms_eps, s));
+            TRY(o3v_gemm_fp8(w.a8, w.sa, lw.gu_w8, lw.gu_s, nullptr, nullptr, w.mlp, rows, 2 * I, H, H, H, I, 0, O3V_EPI_SWIGLU, s));
+            TRY(o3v_quantize_rows_fp8(w.mlp, w.m8, w.sa, rows, I, I, I, s));
+            TRY(o3v_gemm_fp8(w.m8, w.sa, lw.down_w8, lw.down_s, nullptr, x, x, rows, H, I, I, I, H, H, O3V_EPI_RESIDUAL, s));
+        } else {
+            TRY(linear(w.att, lw.o_w, nullptr, x, x, rows, H, QD, QD, H, H, O3V_EPI_RESIDUAL, s, w.splitk, w.splitk_bytes, d->gemm_tile));
+            TRY(o3v_rmsnorm(x, lw.ln2, w.h, rows, H, H, H, d->rms_eps, s));
+            TRY(linear(w.h, lw.gu_w, nullptr, nullptr, w.mlp, rows, 2 * I, H, H, I, 0, O3V_EPI_SWIGLU, s, nullptr, 0, d->gemm_tile));
+            TRY(linear(w.mlp, lw.down_w, nullptr, x, x, rows, H, I, I, H, H, O3V_EPI_RESIDUAL, s, w.splitk, w.splitk_bytes, d->gemm_tile));
+        }
         if (l < n_deep && n_ds > 0)
             TRY(o3v_add_rows(x, o.ds_rows, o.ds_src, (const char*)o.ds_feat + (size_t)l * o.ds_stride * 2, n_ds, H, s));
     }
@@ -402,23 +395,13 @@ extern "C" int o3v_llm_prefill_ex(const o3v_llm_desc* d, void* x, const void* co
 }
 
 namespace {
-int llm_head(const o3v_llm_desc* d, const void* x, int ldx, int rows, void* normed, void* logits, bool fp8_rows, o3v_stream_t s,
-             bool pre_normed = false);
-}
-// bf16 weights always: the head of the prefill, of forward_logits and of the log-prob pass (R:grpo_trainer.py:371-384) -- the fp8
-// rows are DECODE rows (o3v_llm_decode streams them), a log-prob must not depend on how many rows its chunk happens to hold
-extern "C" int o3v_llm_head(const o3v_llm_desc* d, const void* x, int ldx, int rows, void* normed, void* logits,
-                            o3v_stream_t s) {
-    return llm_head(d, x, ldx, rows, normed, logits, false, s, false);
-}
-
-namespace {
+enum Weights { W_BF16, W_FP8_ROWS, W_FP8_FRAGS };  // what the decode linears stream: bf16, fp8 rows (<= 3 rows), fp8 fragments (4..32 rows)
 // pre_normed: `normed` already holds RMSNorm(x; final_norm) (the last down_proj of a batched decode step normalised it, TailNorm)
-int llm_head(const o3v_llm_desc* d, const void* x, int ldx, int rows, void* normed, void* logits, bool fp8_rows, o3v_stream_t s,
-             bool pre_normed) {
+int llm_head(const o3v_llm_desc* d, const void* x, int ldx, int rows, void* normed, void* logits, Weights wf, o3v_stream_t s,
+             bool pre_normed = false) {
     if (!d || !x || !normed || !logits || rows <= 0) return O3V_ERR_ARG;
     const int H = d->hidden;
-    if (fp8_rows && rows >= 4 && rows <= 32 && d->lm_head8p) {  // batched decode on fp8 rows: norm apart, fp8 fragments widened in registers
+    if (wf == W_FP8_FRAGS && rows >= 4 && rows <= 32 && d->lm_head8p) {  // batched decode on fp8 rows: norm apart, fp8 fragments widened in registers
         TRY(o3v_rmsnorm(x, d->final_norm, normed, rows, H, ldx, H, d->rms_eps, s));
         return o3v_linear_decode_fp8_rows(normed, d->lm_head8p, d->lm_head_s, nullptr, nullptr, logits, rows, d->vocab, H, H, d->vocab, 0,
                                           O3V_EPI_NONE, s);
@@ -428,23 +411,23 @@ int llm_head(const o3v_llm_desc* d, const void* x, int ldx, int rows, void* norm
         return o3v_linear_decode(normed, nullptr, 0.f, d->lm_head, d->lm_head_p, nullptr, nullptr, logits, rows, d->vocab, H, H,
                                  d->vocab, 0, O3V_EPI_NONE, s);
     }
-    if (fp8_rows && rows <= 3 && d->lm_head8)  // fp8 head (decode with fp8 weights): half the 1.09 GB
+    if (wf == W_FP8_ROWS && rows <= 3 && d->lm_head8)  // fp8 head (decode with fp8 weights): half the 1.09 GB
         return o3v_linear_decode_fp8(x, d->final_norm, d->rms_eps, d->lm_head8, d->lm_head_s, nullptr, nullptr, logits, rows,
                                      d->vocab, H, ldx, d->vocab, 0, O3V_EPI_NONE, s);
     if (rows <= 8)  // decode / last-token head: RMSNorm fused into the weight-streaming GEMV
         return o3v_linear_decode(x, d->final_norm, d->rms_eps, d->lm_head, d->lm_head_p, nullptr, nullptr, logits, rows,
                                  d->vocab, H, ldx, d->vocab, 0, O3V_EPI_NONE, s);
     TRY(o3v_rmsnorm(x, d->final_norm, normed, rows, H, ldx, H, d->rms_eps, s));
-    for (int r0 = 0; r0 < rows;) {
-        // GEMV groups of <= 8 rows for small row counts; one MFMA GEMM otherwise
-        const int n = (rows > 8) ? rows : rows - r0;
-        TRY(linear((const char*)normed + (size_t)r0 * H * 2, d->lm_head, nullptr, nullptr,
-                   (char*)logits + (size_t)r0 * d->vocab * 2, n, d->vocab, H, H, d->vocab, 0, O3V_EPI_NONE, s));
-        r0 += n;
-    }
-    return O3V_OK;
+    return linear(normed, d->lm_head, nullptr, nullptr, logits, rows, d->vocab, H, H, d->vocab, 0, O3V_EPI_NONE, s);  // > 8 rows: one MFMA GEMM
 }
 }  // namespace
+
+// bf16 weights always: the head of the prefill, of forward_logits and of the log-prob pass (R:grpo_trainer.py:371-384) -- the fp8
+// rows are DECODE rows (o3v_llm_decode streams them), a log-prob must not depend on how many rows its chunk happens to hold
+extern "C" int o3v_llm_head(const o3v_llm_desc* d, const void* x, int ldx, int rows, void* normed, void* logits,
+                            o3v_stream_t s) {
+    return llm_head(d, x, ldx, rows, normed, logits, W_BF16, s, false);
+}
 
 // o3v_sample.hip: the sampler of one step followed by its log-probs
 int o3v_sample_lp_step(const void* logits, void* seen, int* cur_tok, int* finished, int* out_ids, float* margins, const int* eos_ids,
@@ -455,7 +438,7 @@ int o3v_sampling_resolve(const o3v_sampling_opts* so, int step, o3v_samp_x* x);
 
 extern "C" int o3v_llm_decode(const o3v_llm_desc* d, const o3v_decode_state* st, int step0, int n_steps,
                               int skip_last_forward, o3v_stream_t s) {
-    return o3v_llm_decode_lp(d, st, nullptr, step0, n_steps, skip_last_forward, s);
+    return o3v_llm_decode_ex(d, st, nullptr, nullptr, step0, n_steps, skip_last_forward, s);
 }
 
 extern "C" int o3v_llm_decode_lp(const o3v_llm_desc* d, const o3v_decode_state* st, const o3v_logprob_opts* lp, int step0,
@@ -463,15 +446,219 @@ extern "C" int o3v_llm_decode_lp(const o3v_llm_desc* d, const o3v_decode_state* 
     return o3v_llm_decode_ex(d, st, lp, nullptr, step0, n_steps, skip_last_forward, s);
 }
 
+namespace {
+// Which kernels the steps of one decode call launch; layer 0's weights speak for the stack.  Set and explained in decide_regime().
+struct Regime {
+    Weights weights, qkv_weights;                     // of the linears; of q/k/v
+    bool norm_apart, qkv_fused_norm, qk_norm, group;  // fixed for the call
+    bool block, layer_block, tail;                    // tried, may fall back: see settle()
+};
+// The one rule of the try-then-fall-back forms: O3V_ERR_SHAPE from the FIRST launch of a form in a call (layer 0 of its first step)
+// switches the form off for the rest of the call; any other non-OK code, and O3V_ERR_SHAPE later on, is returned.  Every such condition
+// of o3v_decode_attn_block*, o3v_decode_layer_block and o3v_linear_decode_norm_next is a constant of the call (shapes, device, residency).
+int settle(bool& on, bool first, int rc) {
+    if (rc != O3V_ERR_SHAPE || !first) return rc;
+    on = false;
+    return O3V_OK;
+}
+// the only reader of st->flags, st->sync, st->group and of the fp8 / fragment / q_norm pointers for the choice of kernels
+Regime decide_regime(const o3v_llm_desc* d, const o3v_decode_state* st) {
+    const int B = st->B, H = d->hidden;
+    const o3v_llm_layer_w& l0 = d->layer[0];
+    Regime r;
+    // B >= 4 rows run on the matrix-core linears, which stage the normalised x of a fused RMSNorm in LDS (57 KB at B=8, 115 KB
+    // at B=16: two blocks, then one, per CU).  With a separate 3 us norm launch the linears are LDS-free: gate/up 54 -> 44 us
+    // at B=8, 75 -> 50 us at B=16 (profiles/r01_m8_linear.txt).  Whole step, 7B: B=4 3.56 -> 3.61 ms (worse: two more
+    // launches per layer), B=8 4.04 -> 3.97, B=16 5.63 -> 5.25: taken from B=8 on.
+    r.norm_apart = B >= 8;  // (above 16 rows the linears take no fused norm at all)
+    // ... except q/k/v at 8 rows: its grid is ~1 workgroup per CU (288 at 7B), so the LDS the fused norm stages x in costs no
+    // residency, and the prologue replaces a 5.9 us launch.  Same sums, same rounding as o3v_rmsnorm: bit-identical.  Measured
+    // (7B, G rows of one prompt, ms/step fused | apart): G=8 3.721 | 3.768, G=16 4.365 | 4.312 -- taken at 8 rows only.
+    r.qkv_fused_norm = r.norm_apart && B <= 8 && !(st->flags & O3V_DECODE_NO_QKV_FUSED_NORM) && (size_t)B * (H * 2 + 16) <= 144 * 1024;
+    // fp8 weights (batch <= 3): every decode linear streams the fp8 copy
+    const bool fp8 = B <= 3 && l0.qkv_w8 && l0.o_w8 && l0.gu_w8 && l0.down_w8 && st->group <= 1;
+    // fp8 rows at 4..32 rows (BASELINE config #5: N = 16 chains on fp8 weights): norms run apart, the linears stream the
+    // fragment-major fp8 images
+    const bool fp8b = B >= 4 && l0.gu_w8p && l0.down_w8p && l0.o_w8p;
+    r.weights = fp8 ? W_FP8_ROWS : fp8b ? W_FP8_FRAGS : W_BF16;
+    r.qkv_weights = fp8b && !l0.qkv_w8p ? W_BF16 : r.weights;  // (without a fragment image of its own q/k/v stays on the bf16 weights)
+    r.qk_norm = l0.q_norm != nullptr;  // Qwen3-VL: per-head RMSNorm between the q/k/v linear and the rotation
+    r.group = st->group > 1;           // the rows of a group share the prompt K/V: read it once per group
+    // batch 1: q/k/v + attention + merge + o_proj as ONE launch (o3v_fused.hip); epoch = index of the launch in this generate call
+    r.block = st->sync && B == 1 && st->group <= 1 && st->nsplit > 0;
+    // the persistent layer block (attention half + gate/up in one launch): bf16 rows, no q/k norm
+    r.layer_block = r.block && (st->flags & O3V_DECODE_LAYER_BLOCK) && !fp8 && !r.qk_norm;
+    // 8..32 bf16 rows: the residual linears normalise for the linear that follows (o3v_linear_decode_norm_next), so only layer 0's
+    // first norm of a step is a launch of its own.  O3V_DECODE_NO_TAIL_NORM switches it off (A/B, tests).
+    r.tail = r.norm_apart && !fp8b && st->sync && !(st->flags & O3V_DECODE_NO_TAIL_NORM) && d->lm_head_p && l0.o_wp && l0.down_wp;
+    return r;
+}
+
+// One decode call: its regime, what its step functions share (workspace, dimensions, strides, the running step) and the hand-overs
+struct Decode {
+    const o3v_llm_desc* d;
+    const o3v_decode_state* st;
+    o3v_stream_t s;
+    Regime r;
+    // host_stats (optional, host memory): [0] += decode forwards, [1] += kernel launches inside their layer loops, [2] += layers whose
+    // attention half ran as the one-launch block, [3] += layers whose attention half ran on the stand-alone kernels
+    long long* hs;
+    int step0, step, B, H, Hq, Hkv, D, I, V, QD, NQKV, slot0;
+    LlmWs w;
+    float scale;
+    size_t layer_stride, pre_stride;
+    // The "already normalised" hand-overs of a forward (TailNorm).  Whatever rewrites x (a new token's embedding, a residual linear)
+    // calls x_changed(); the o3v_linear_decode_norm_next launch that did it then sets the one it wrote.
+    bool h_ready;       // w.h holds RMSNorm(x; ln1 of the layer about to run)
+    bool h2_ready;      // w.h holds RMSNorm(x; ln2 of the running layer)
+    bool normed_ready;  // w.normed holds RMSNorm(x; final_norm)
+    void x_changed() { h_ready = h2_ready = normed_ready = false; }
+    char* kc(int l) const { return (char*)st->kcache + l * layer_stride; }
+    char* vc(int l) const { return (char*)st->vcache + l * layer_stride; }
+    uint32_t epoch(int l) const { return (uint32_t)(step * d->layers + l + 1); }  // of the one-launch forms
+    bool first(int l) const { return l == 0 && step == step0; }                   // the launch at which settle() may switch a form off
+    int sample(const o3v_logprob_opts* lp, const o3v_sampling_opts* so) {
+        // so: the extended sampler kernels on this step's controls, then (lp given) its log-probs
+        // lp alone: the same sampler, then the log-probs of what it drew (sampling: the embedding row is gathered below as usual)
+        o3v_samp_x sx;
+        if (so) TRY(o3v_sampling_resolve(so, step, &sx));
+        if (so || lp)
+            return o3v_sample_lp_step(st->logits, st->seen, st->cur_tok, st->finished, st->out_ids, st->margins, st->eos_ids, st->n_eos,
+                                      st->pad_id, B, V, V, st->do_sample, st->rep_penalty, st->temperature, st->top_k, st->top_p, st->seed,
+                                      st->row_id, step, st->Tnew, st->sample_scratch, st->do_sample ? nullptr : d->embed, st->x, H, lp,
+                                      so ? &sx : nullptr, s);
+        if (st->do_sample)
+            return o3v_sample_top_k_top_p(st->logits, st->seen, st->cur_tok, st->finished, st->out_ids, st->margins, st->eos_ids,
+                                          st->n_eos, st->pad_id, B, V, V, st->rep_penalty, st->temperature, st->top_k, st->top_p,
+                                          st->seed, st->row_id, step, st->Tnew, st->sample_scratch, s);
+        // greedy: the chosen token's embedding row is gathered by the sampler's last stage
+        return o3v_sample_greedy_embed(st->logits, st->seen, st->cur_tok, st->finished, st->out_ids, st->margins, st->eos_ids,
+                                       st->n_eos, st->pad_id, B, V, V, st->rep_penalty, step, st->Tnew, st->sample_scratch,
+                                       d->embed, st->x, H, s);
+    }
+    // one decode linear [B,K] -> [B,N] on the weight form wf (W / Wp, W8 + sc, W8p + sc); O3V_EPI_RESIDUAL adds to x.  ln given: the
+    // RMSNorm of X is fused -- never on fp8 fragments, whose X arrives normalised
+    int lin(Weights wf, const void* X, const void* ln, const void* W, const void* Wp, const void* W8, const void* W8p, const float* sc,
+            const void* bias, void* out, int N, int K, int ldo, int epi) {
+        const void* res = epi == O3V_EPI_RESIDUAL ? st->x : nullptr;
+        const float eps = ln ? d->rms_eps : 0.f;
+        if (wf == W_FP8_ROWS) return o3v_linear_decode_fp8(X, ln, eps, W8, sc, bias, res, out, B, N, K, K, ldo, res ? H : 0, epi, s);
+        if (wf == W_FP8_FRAGS) return o3v_linear_decode_fp8_rows(X, W8p, sc, bias, res, out, B, N, K, K, ldo, res ? H : 0, epi, s);
+        return o3v_linear_decode(X, ln, eps, W, Wp, bias, res, out, B, N, K, K, ldo, res ? H : 0, epi, s);
+    }
+    // q/k/v (+norm, rope, cache append) of layer l
+    int qkv(int l, const o3v_llm_layer_w& lw) {
+        const Weights wf = r.qkv_weights;
+        // the norm in front as a launch of its own: always on fp8 fragments; on bf16 rows where norms run apart, unless handed over
+        const bool apart = wf == W_FP8_FRAGS || (r.norm_apart && !r.qkv_fused_norm);
+        if (apart && (wf == W_FP8_FRAGS || !h_ready)) TRY(o3v_rmsnorm(st->x, lw.ln1, w.h, B, H, H, H, d->rms_eps, s));
+        const void *xin = apart ? w.h : st->x, *ln = apart ? nullptr : lw.ln1;  // normalised x, or x and the norm to fuse
+        if (r.qk_norm) {
+            TRY(lin(wf, xin, ln, lw.qkv_w, lw.qkv_wp, lw.qkv_w8, lw.qkv_w8p, lw.qkv_s, lw.qkv_b, w.qkv, NQKV, H, NQKV, O3V_EPI_NONE));
+            return o3v_qkv_norm_rope_cache(w.qkv, lw.q_norm, lw.k_norm, d->rms_eps, st->cosT, st->sinT, w.q, kc(l), vc(l), slot0 + step, B, 1,
+                                           Hq, Hkv, D, st->Tmax, st->Tnew, step, s);
+        }
+        if (wf == W_FP8_FRAGS)
+            return o3v_qkv_rope_fp8_rows(w.h, lw.qkv_w8p, lw.qkv_s, lw.qkv_b, B, H, H, st->cosT, st->sinT, w.q, kc(l), vc(l), slot0 + step, Hq,
+                                         Hkv, D, st->Tmax, st->Tnew, step, s);
+        if (wf == W_FP8_ROWS)
+            return o3v_gemv_norm_qkv_rope_fp8(st->x, lw.ln1, d->rms_eps, lw.qkv_w8, lw.qkv_s, lw.qkv_b, B, H, H, st->cosT, st->sinT, w.q,
+                                              kc(l), vc(l), slot0 + step, Hq, Hkv, D, st->Tmax, st->Tnew, step, s);
+        return o3v_gemv_norm_qkv_rope(xin, ln, ln ? d->rms_eps : 0.f, lw.qkv_w, lw.qkv_wp, lw.qkv_b, B, H, H, st->cosT, st->sinT, w.q, kc(l),
+                                      vc(l), slot0 + step, Hq, Hkv, D, st->Tmax, st->Tnew, step, s);
+    }
+    // attention + merge of layer l on the stand-alone kernels
+    int attention(int l) {
+        if (r.group)
+            return o3v_attn_decode_group_prefix(w.q, kc(l), vc(l), st->kprefix ? (const char*)st->kprefix + l * pre_stride : nullptr,
+                                                st->kprefix ? (const char*)st->vprefix + l * pre_stride : nullptr, st->prefix_cap,
+                                                st->rows_per_prompt, w.att, st->part_o, st->part_ml, st->k_lo, B, st->group, Hq, Hkv, D,
+                                                st->S, st->S + step + 1, st->Tmax, st->nsplit, scale, s);
+        return o3v_attn_decode(w.q, kc(l), vc(l), w.att, st->part_o, st->part_ml, st->k_lo, B, Hq, Hkv, D, st->S + step + 1, st->Tmax,
+                               st->nsplit, scale, s);
+    }
+    // o_proj + residual of layer l (TailNorm: and the norm in front of gate/up)
+    int o_proj(int l, const o3v_llm_layer_w& lw) {
+        x_changed();
+        if (r.tail) {
+            const uint32_t ep = (uint32_t)(step * d->layers + l) * 2u + 1u;
+            TRY(settle(r.tail, first(l), o3v_linear_decode_norm_next(w.att, lw.o_wp, st->x, st->x, B, H, QD, QD, H, H, lw.ln2, d->rms_eps, w.h, H,
+                                                                     st->sync, ep, s)));
+            if ((h2_ready = r.tail)) return O3V_OK;  // else not this device / these shapes: two launches, for the whole call
+        }
+        return lin(r.weights, w.att, nullptr, lw.o_w, lw.o_wp, lw.o_w8, lw.o_w8p, lw.o_s, nullptr, st->x, H, QD, H, O3V_EPI_RESIDUAL);
+    }
+    // MLP half of layer l: (norm,) gate/up + SwiGLU, down_proj + residual (TailNorm: and the norm in front of the next linear)
+    int mlp(int l, const o3v_llm_layer_w& lw) {
+        const bool frags = r.weights == W_FP8_FRAGS, apart = frags || r.norm_apart;
+        if (apart && (frags || !h2_ready)) TRY(o3v_rmsnorm(st->x, lw.ln2, w.h, B, H, H, H, d->rms_eps, s));
+        TRY(lin(r.weights, apart ? w.h : st->x, apart ? nullptr : lw.ln2, lw.gu_w, lw.gu_wp, lw.gu_w8, lw.gu_w8p, lw.gu_s, nullptr, w.mlp, 2 * I,
+                H, I, O3V_EPI_SWIGLU));
+        return down_proj(l, lw);
+    }
+    int down_proj(int l, const o3v_llm_layer_w& lw) {  // also behind the layer block
+        x_changed();
+        if (r.tail) {  // down_proj + the next layer's first norm (the head's norm after the last layer)
+            const bool last = l + 1 == d->layers;
+            const uint32_t ep = (uint32_t)(step * d->layers + l) * 2u + 2u;
+            TRY(o3v_linear_decode_norm_next(w.mlp, lw.down_wp, st->x, st->x, B, H, I, I, H, H, last ? d->final_norm : d->layer[l + 1].ln1,
+                                            d->rms_eps, last ? w.normed : w.h, H, st->sync, ep, s));
+            (last ? normed_ready : h_ready) = true;
+            return O3V_OK;
+        }
+        return lin(r.weights, w.mlp, nullptr, lw.down_w, lw.down_wp, lw.down_w8, lw.down_w8p, lw.down_s, nullptr, st->x, H, I, H,
+                   O3V_EPI_RESIDUAL);
+    }
+    // attention half of layer l: the one-launch block, or q/k/v, attention + merge and o_proj as stand-alone launches
+    int attention_half(int l, const o3v_llm_layer_w& lw) {
+        const bool fp8 = r.weights == W_FP8_ROWS;
+        if (r.block) {
+            const int rc =
+                r.qk_norm ? o3v_decode_attn_block_qknorm(st->x, lw.ln1, d->rms_eps, fp8 ? lw.qkv_w8 : lw.qkv_w, fp8 ? lw.qkv_s : nullptr,
+                                                         fp8 ? lw.o_w8 : lw.o_w, fp8 ? lw.o_s : nullptr, lw.q_norm, lw.k_norm, w.qkv,
+                                                         st->cosT, st->sinT, w.q, w.att, kc(l), vc(l), st->part_o, st->part_ml, st->k_lo, H,
+                                                         Hq, Hkv, D, st->S + step, st->Tmax, st->Tnew, step, st->nsplit, scale, st->sync,
+                                                         epoch(l), s)
+                : fp8 ? o3v_decode_attn_block_fp8(st->x, lw.ln1, d->rms_eps, lw.qkv_w8, lw.qkv_s, lw.qkv_b, lw.o_w8, lw.o_s, st->cosT,
+                                                  st->sinT, w.q, w.att, kc(l), vc(l), st->part_o, st->part_ml, st->k_lo, H, Hq, Hkv, D,
+                                                  st->S + step, st->Tmax, st->Tnew, step, st->nsplit, scale, st->sync, epoch(l), s)
+                      : o3v_decode_attn_block(st->x, lw.ln1, d->rms_eps, lw.qkv_w, lw.qkv_b, lw.o_w, st->cosT, st->sinT, w.q, w.att,
+                                              kc(l), vc(l), st->part_o, st->part_ml, st->k_lo, H, Hq, Hkv, D, st->S + step, st->Tmax,
+                                              st->Tnew, step, st->nsplit, scale, st->sync, epoch(l), s);
+            TRY(settle(r.block, first(l), rc));  // off: shapes or residency do not allow the one-launch form: the stand-alone kernels instead
+        }
+        if (!r.block) {
+            TRY(qkv(l, lw));
+            TRY(attention(l));
+            TRY(o_proj(l, lw));
+        }
+        if (hs) ++hs[r.block ? 2 : 3];
+        return O3V_OK;
+    }
+    int layer(int l) {
+        const o3v_llm_layer_w& lw = d->layer[l];
+        if (r.layer_block) {
+            TRY(settle(r.layer_block, first(l),
+                       o3v_decode_layer_block(st->x, lw.ln1, d->rms_eps, lw.qkv_w, lw.qkv_b, lw.o_w, lw.ln2, lw.gu_w, w.mlp, st->cosT,
+                                              st->sinT, w.q, w.att, kc(l), vc(l), st->part_o, st->part_ml, st->k_lo, H, I, Hq, Hkv, D,
+                                              st->S + step, st->Tmax, st->Tnew, step, st->nsplit, scale, st->sync, epoch(l), s)));
+            if (r.layer_block) {
+                if (hs) ++hs[2];
+                return down_proj(l, lw);
+            }  // off: shapes or residency: the role-per-workgroup block (or the stand-alone kernels) instead
+        }
+        TRY(attention_half(l, lw));
+        return mlp(l, lw);
+    }
+};
+}  // namespace
+
 extern "C" int o3v_llm_decode_ex(const o3v_llm_desc* d, const o3v_decode_state* st, const o3v_logprob_opts* lp,
                                  const o3v_sampling_opts* so, int step0, int n_steps, int skip_last_forward, o3v_stream_t s) {
-    if (so) {  // host-only checks of the controls, before anything else
-        o3v_samp_x probe;
-        const int rc = o3v_sampling_resolve(so, 0, &probe);
-        if (rc != O3V_OK) return rc;
-    }
+    o3v_samp_x probe;
+    if (so) TRY(o3v_sampling_resolve(so, 0, &probe));  // host-only checks of the controls, before anything else
     if (!d || !st || !st->x || !st->kcache || !st->vcache || !st->cosT || !st->sinT || !st->logits || !st->seen ||
-        !st->cur_tok || !st->finished || !st->out_ids || !st->part_o || !st->part_ml || !st->workspace)
+        !st->cur_tok || !st->finished || !st->out_ids || !st->part_o || !st->part_ml || !st->workspace || !st->sample_scratch)
         return O3V_ERR_ARG;
     const int B = st->B;
     // shared prompt entries: the caches hold only the generated tokens (slot = step), the prompt K/V live once per prompt
@@ -481,217 +668,30 @@ extern "C" int o3v_llm_decode_ex(const o3v_llm_desc* d, const o3v_decode_state* 
         return O3V_ERR_ARG;
     if (pfx && (!st->vprefix || st->group <= 1 || st->rows_per_prompt <= 0 || (B % st->rows_per_prompt) || st->S > st->prefix_cap))
         return O3V_ERR_ARG;
-    const int slot0 = pfx ? 0 : st->S;  // cache slot of generated token 0
-    if (!st->sample_scratch) return O3V_ERR_ARG;
-    const int H = d->hidden, Hq = d->heads, Hkv = d->kv_heads, D = d->head_dim, I = d->inter, V = d->vocab;
-    const int QD = Hq * D, NQKV = (Hq + 2 * Hkv) * D;
-    LlmWs w;
-    if (st->ws_bytes < o3v_llm_workspace_bytes(d, B) || !carve_llm(d, B, st->workspace, st->ws_bytes, w))
+    Decode c{d, st, s, decide_regime(d, st), (long long*)st->host_stats, step0};
+    c.B = B, c.H = d->hidden, c.Hq = d->heads, c.Hkv = d->kv_heads, c.D = d->head_dim, c.I = d->inter, c.V = d->vocab;
+    c.QD = c.Hq * c.D, c.NQKV = (c.Hq + 2 * c.Hkv) * c.D, c.slot0 = pfx ? 0 : st->S;  // slot0: cache slot of generated token 0
+    if (st->ws_bytes < o3v_llm_workspace_bytes(d, B) || !carve_llm(d, B, st->workspace, st->ws_bytes, c.w))
         return O3V_ERR_WORKSPACE;
-    const float scale = 1.0f / sqrtf((float)D);
-    const size_t layer_stride = (size_t)B * Hkv * st->Tmax * D * 2;
-    const size_t pre_stride = pfx ? (size_t)(B / st->rows_per_prompt) * Hkv * st->prefix_cap * D * 2 : 0;
-    // B >= 4 rows run on the matrix-core linears, which stage the normalised x of a fused RMSNorm in LDS (57 KB at B=8, 115 KB
-    // at B=16: two blocks, then one, per CU).  With a separate 3 us norm launch the linears are LDS-free: gate/up 54 -> 44 us
-    // at B=8, 75 -> 50 us at B=16 (profiles/r01_m8_linear.txt).  Whole step, 7B: B=4 3.56 -> 3.61 ms (worse: two more
-    // launches per layer), B=8 4.04 -> 3.97, B=16 5.63 -> 5.25: taken from B=8 on.
-    const bool norm_apart = B >= 8;
-    // ... except q/k/v at 8 rows: its grid is ~1 workgroup per CU (288 at 7B), so the LDS the fused norm stages x in costs no
-    // residency, and the prologue replaces a 5.9 us launch.  Same sums, same rounding as o3v_rmsnorm: bit-identical.  Measured
-    // (7B, G rows of one prompt, ms/step fused | apart): G=8 3.721 | 3.768, G=16 4.365 | 4.312 -- taken at 8 rows only.
-    const bool qkv_fused_norm = norm_apart && B <= 8 && !(st->flags & 4) && (size_t)B * (H * 2 + 16) <= 144 * 1024;
-    // batch 1: q/k/v + attention + merge + o_proj as ONE launch (o3v_fused.hip); epoch = index of the launch in this generate call
-    // fp8 weights (batch <= 3): every decode linear streams the fp8 copy
-    const bool fp8 = B <= 3 && d->layer[0].qkv_w8 && d->layer[0].o_w8 && d->layer[0].gu_w8 && d->layer[0].down_w8 && st->group <= 1;
-    // fp8 rows at 4..32 rows (BASELINE config #5: N = 16 chains on fp8 weights): norms run apart, the linears stream the
-    // fragment-major fp8 images
-    const bool fp8b = B >= 4 && d->layer[0].gu_w8p && d->layer[0].down_w8p && d->layer[0].o_w8p;
-    const bool qk_norm = d->layer[0].q_norm != nullptr;  // Qwen3-VL: per-head RMSNorm between the q/k/v linear and the rotation
-    bool fused = st->sync && B == 1 && st->group <= 1 && st->nsplit > 0;
-    // the persistent layer block (attention half + gate/up in one launch): bf16 rows, no q/k norm
-    bool layer_block = fused && (st->flags & 1) && !fp8 && !qk_norm;
-    int step = step0;
-    // 8..32 bf16 rows: the residual linears normalise for the linear that follows (o3v_linear_decode_norm_next), so only layer 0's
-    // first norm of a step is a launch of its own.  st->flags & 2 switches it off (A/B, tests).
-    bool tail = norm_apart && !fp8b && st->sync && !(st->flags & 2) && d->lm_head_p && d->layer[0].o_wp && d->layer[0].down_wp;
-    bool h_ready = false;       // w.h holds RMSNorm(x; ln1 of the layer about to run)
-    bool h2_ready = false;      // w.h holds RMSNorm(x; ln2 of the running layer)
-    bool normed_ready = false;  // w.normed holds RMSNorm(x; final_norm)
-    // host_stats (optional, host memory): [0] += decode forwards, [1] += kernel launches inside their layer loops, [2] += layers whose
-    // attention half ran as the one-launch block, [3] += layers whose attention half ran on the stand-alone kernels
-    long long* hs = (long long*)st->host_stats;
-    // attention half of layer l as stand-alone launches: q/k/v (+norm, rope, cache append), attention + merge, o_proj + residual
-    auto attention_half = [&](int l) -> int {
-        const o3v_llm_layer_w& lw = d->layer[l];
-        char* kc = (char*)st->kcache + l * layer_stride;
-        char* vc = (char*)st->vcache + l * layer_stride;
-        if (qk_norm) {
-            if (fp8)
-                TRY(o3v_linear_decode_fp8(st->x, lw.ln1, d->rms_eps, lw.qkv_w8, lw.qkv_s, lw.qkv_b, nullptr, w.qkv, B, NQKV, H, H, NQKV, 0,
-                                          O3V_EPI_NONE, s));
-            else if (fp8b && lw.qkv_w8p) {
-                TRY(o3v_rmsnorm(st->x, lw.ln1, w.h, B, H, H, H, d->rms_eps, s));
-                TRY(o3v_linear_decode_fp8_rows(w.h, lw.qkv_w8p, lw.qkv_s, lw.qkv_b, nullptr, w.qkv, B, NQKV, H, H, NQKV, 0, O3V_EPI_NONE, s));
-            } else if (norm_apart && !qkv_fused_norm) {  // (above 16 rows the linears take no fused norm at all)
-                if (!h_ready) TRY(o3v_rmsnorm(st->x, lw.ln1, w.h, B, H, H, H, d->rms_eps, s));
-                TRY(o3v_linear_decode(w.h, nullptr, 0.f, lw.qkv_w, lw.qkv_wp, lw.qkv_b, nullptr, w.qkv, B, NQKV, H, H, NQKV, 0, O3V_EPI_NONE, s));
-            } else
-                TRY(o3v_linear_decode(st->x, lw.ln1, d->rms_eps, lw.qkv_w, lw.qkv_wp, lw.qkv_b, nullptr, w.qkv, B, NQKV, H, H, NQKV, 0,
-                                      O3V_EPI_NONE, s));
-            TRY(o3v_qkv_norm_rope_cache(w.qkv, lw.q_norm, lw.k_norm, d->rms_eps, st->cosT, st->sinT, w.q, kc, vc, slot0 + step, B, 1, Hq,
-                                        Hkv, D, st->Tmax, st->Tnew, step, s));
-        } else if (fp8b && lw.qkv_w8p) {
-            TRY(o3v_rmsnorm(st->x, lw.ln1, w.h, B, H, H, H, d->rms_eps, s));
-            TRY(o3v_qkv_rope_fp8_rows(w.h, lw.qkv_w8p, lw.qkv_s, lw.qkv_b, B, H, H, st->cosT, st->sinT, w.q, kc, vc, slot0 + step, Hq, Hkv, D,
-                                      st->Tmax, st->Tnew, step, s));
-        } else if (fp8) {
-            TRY(o3v_gemv_norm_qkv_rope_fp8(st->x, lw.ln1, d->rms_eps, lw.qkv_w8, lw.qkv_s, lw.qkv_b, B, H, H, st->cosT, st->sinT, w.q,
-                                           kc, vc, slot0 + step, Hq, Hkv, D, st->Tmax, st->Tnew, step, s));
-        } else if (norm_apart && !qkv_fused_norm) {
-            if (!h_ready) TRY(o3v_rmsnorm(st->x, lw.ln1, w.h, B, H, H, H, d->rms_eps, s));
-            TRY(o3v_gemv_norm_qkv_rope(w.h, nullptr, 0.f, lw.qkv_w, lw.qkv_wp, lw.qkv_b, B, H, H, st->cosT, st->sinT, w.q, kc, vc,
-                                       slot0 + step, Hq, Hkv, D, st->Tmax, st->Tnew, step, s));
-        } else {
-            TRY(o3v_gemv_norm_qkv_rope(st->x, lw.ln1, d->rms_eps, lw.qkv_w, lw.qkv_wp, lw.qkv_b, B, H, H, st->cosT, st->sinT, w.q,
-                                       kc, vc, slot0 + step, Hq, Hkv, D, st->Tmax, st->Tnew, step, s));
-        }
-        if (st->group > 1)  // the rows of a group share the prompt K/V: read it once per group
-            TRY(o3v_attn_decode_group_prefix(w.q, kc, vc, pfx ? (const char*)st->kprefix + l * pre_stride : nullptr,
-                                             pfx ? (const char*)st->vprefix + l * pre_stride : nullptr, st->prefix_cap,
-                                             st->rows_per_prompt, w.att, st->part_o, st->part_ml, st->k_lo, B, st->group, Hq, Hkv, D,
-                                             st->S, st->S + step + 1, st->Tmax, st->nsplit, scale, s));
-        else
-            TRY(o3v_attn_decode(w.q, kc, vc, w.att, st->part_o, st->part_ml, st->k_lo, B, Hq, Hkv, D, st->S + step + 1, st->Tmax,
-                                st->nsplit, scale, s));
-        if (fp8)
-            TRY(o3v_linear_decode_fp8(w.att, nullptr, 0.f, lw.o_w8, lw.o_s, nullptr, st->x, st->x, B, H, QD, QD, H, H, O3V_EPI_RESIDUAL, s));
-        else if (fp8b)
-            TRY(o3v_linear_decode_fp8_rows(w.att, lw.o_w8p, lw.o_s, nullptr, st->x, st->x, B, H, QD, QD, H, H, O3V_EPI_RESIDUAL, s));
-        else {
-            h_ready = h2_ready = false;
-            if (tail) {
-                const uint32_t epoch = (uint32_t)(step * d->layers + l) * 2u + 1u;
-                const int rc = o3v_linear_decode_norm_next(w.att, lw.o_wp, st->x, st->x, B, H, QD, QD, H, H, lw.ln2, d->rms_eps, w.h, H,
-                                                           st->sync, epoch, s);
-                if (rc == O3V_OK) {
-                    h2_ready = true;
-                    return O3V_OK;
-                }
-                if (rc != O3V_ERR_SHAPE || l != 0 || step != step0) return rc;
-                tail = false;  // not this device / these shapes: two launches, for the whole call
-            }
-            TRY(o3v_linear_decode(w.att, nullptr, 0.f, lw.o_w, lw.o_wp, nullptr, st->x, st->x, B, H, QD, QD, H, H, O3V_EPI_RESIDUAL, s));
-        }
-        return O3V_OK;
-    };
+    c.scale = 1.0f / sqrtf((float)c.D);
+    c.layer_stride = (size_t)B * c.Hkv * st->Tmax * c.D * 2;
+    c.pre_stride = pfx ? (size_t)(B / st->rows_per_prompt) * c.Hkv * st->prefix_cap * c.D * 2 : 0;
     for (int i = 0; i < n_steps; ++i) {
-        step = step0 + i;
-        if (so) {  // the extended sampler kernels on this step's controls, then (lp given) its log-probs
-            o3v_samp_x sx;
-            TRY(o3v_sampling_resolve(so, step, &sx));
-            TRY(o3v_sample_lp_step(st->logits, st->seen, st->cur_tok, st->finished, st->out_ids, st->margins, st->eos_ids, st->n_eos,
-                                   st->pad_id, B, V, V, st->do_sample, st->rep_penalty, st->temperature, st->top_k, st->top_p, st->seed,
-                                   st->row_id, step, st->Tnew, st->sample_scratch, st->do_sample ? nullptr : d->embed, st->x, H, lp,
-                                   &sx, s));
-        } else if (lp)  // the same sampler, then the log-probs of what it drew (sampling: the embedding row is gathered below as usual)
-            TRY(o3v_sample_lp_step(st->logits, st->seen, st->cur_tok, st->finished, st->out_ids, st->margins, st->eos_ids, st->n_eos,
-                                   st->pad_id, B, V, V, st->do_sample, st->rep_penalty, st->temperature, st->top_k, st->top_p, st->seed,
-                                   st->row_id, step, st->Tnew, st->sample_scratch, st->do_sample ? nullptr : d->embed, st->x, H, lp,
-                                   nullptr, s));
-        else if (st->do_sample)
-            TRY(o3v_sample_top_k_top_p(st->logits, st->seen, st->cur_tok, st->finished, st->out_ids, st->margins, st->eos_ids,
-                                       st->n_eos, st->pad_id, B, V, V, st->rep_penalty, st->temperature, st->top_k, st->top_p,
-                                       st->seed, st->row_id, step, st->Tnew, st->sample_scratch, s));
-        else  // greedy: the chosen token's embedding row is gathered by the sampler's last stage
-            TRY(o3v_sample_greedy_embed(st->logits, st->seen, st->cur_tok, st->finished, st->out_ids, st->margins, st->eos_ids,
-                                        st->n_eos, st->pad_id, B, V, V, st->rep_penalty, step, st->Tnew, st->sample_scratch,
-                                        d->embed, st->x, H, s));
+        c.step = step0 + i;
+        TRY(c.sample(lp, so));
         if (skip_last_forward && i == n_steps - 1) break;
-        if (slot0 + step >= st->Tmax) return O3V_ERR_ARG;
+        if (c.slot0 + c.step >= st->Tmax) return O3V_ERR_ARG;
         // one decode forward: token `step` sits in cache slot S+step, context = S+step+1 keys
-        if (st->do_sample) TRY(o3v_embed_tokens(d->embed, st->cur_tok, st->x, B, H, s));
-        h_ready = h2_ready = normed_ready = false;  // x is the sampler's embedding row
+        if (st->do_sample) TRY(o3v_embed_tokens(d->embed, st->cur_tok, st->x, B, c.H, s));
+        c.x_changed();  // x is the sampler's embedding row
         const long long launches0 = o3v_tl_launches;
-        for (int l = 0; l < d->layers; ++l) {
-            const o3v_llm_layer_w& lw = d->layer[l];
-            char* kc = (char*)st->kcache + l * layer_stride;
-            char* vc = (char*)st->vcache + l * layer_stride;
-            if (layer_block) {
-                const uint32_t epoch = (uint32_t)(step * d->layers + l + 1);
-                const int rc = o3v_decode_layer_block(st->x, lw.ln1, d->rms_eps, lw.qkv_w, lw.qkv_b, lw.o_w, lw.ln2, lw.gu_w, w.mlp, st->cosT,
-                                                      st->sinT, w.q, w.att, kc, vc, st->part_o, st->part_ml, st->k_lo, H, I, Hq, Hkv, D,
-                                                      st->S + step, st->Tmax, st->Tnew, step, st->nsplit, scale, st->sync, epoch, s);
-                if (rc == O3V_ERR_SHAPE && l == 0 && step == step0) {
-                    layer_block = false;  // shapes or residency: the role-per-workgroup block (or the stand-alone kernels) instead
-                } else if (rc != O3V_OK) {
-                    return rc;
-                } else {
-                    if (hs) ++hs[2];
-                    TRY(o3v_linear_decode(w.mlp, nullptr, 0.f, lw.down_w, lw.down_wp, nullptr, st->x, st->x, B, H, I, I, H, H,
-                                          O3V_EPI_RESIDUAL, s));
-                    continue;
-                }
-            }
-            if (fused) {
-                const uint32_t epoch = (uint32_t)(step * d->layers + l + 1);
-                const int rc =
-                    qk_norm ? o3v_decode_attn_block_qknorm(st->x, lw.ln1, d->rms_eps, fp8 ? lw.qkv_w8 : lw.qkv_w, fp8 ? lw.qkv_s : nullptr,
-                                                           fp8 ? lw.o_w8 : lw.o_w, fp8 ? lw.o_s : nullptr, lw.q_norm, lw.k_norm, w.qkv,
-                                                           st->cosT, st->sinT, w.q, w.att, kc, vc, st->part_o, st->part_ml, st->k_lo, H, Hq,
-                                                           Hkv, D, st->S + step, st->Tmax, st->Tnew, step, st->nsplit, scale, st->sync,
-                                                           epoch, s)
-                    : fp8 ? o3v_decode_attn_block_fp8(st->x, lw.ln1, d->rms_eps, lw.qkv_w8, lw.qkv_s, lw.qkv_b, lw.o_w8, lw.o_s, st->cosT,
-                                                    st->sinT, w.q, w.att, kc, vc, st->part_o, st->part_ml, st->k_lo, H, Hq, Hkv, D,
-                                                    st->S + step, st->Tmax, st->Tnew, step, st->nsplit, scale, st->sync, epoch, s)
-                        : o3v_decode_attn_block(st->x, lw.ln1, d->rms_eps, lw.qkv_w, lw.qkv_b, lw.o_w, st->cosT, st->sinT, w.q, w.att, kc,
-                                                vc, st->part_o, st->part_ml, st->k_lo, H, Hq, Hkv, D, st->S + step, st->Tmax, st->Tnew,
-                                                step, st->nsplit, scale, st->sync, epoch, s);
-                if (rc == O3V_ERR_SHAPE && l == 0)
-                    fused = false;  // shapes or residency do not allow the one-launch form: the stand-alone kernels instead
-                else if (rc != O3V_OK)
-                    return rc;
-            }
-            if (!fused) TRY(attention_half(l));
-            if (hs) ++hs[fused ? 2 : 3];
-            if (fp8) {
-                TRY(o3v_linear_decode_fp8(st->x, lw.ln2, d->rms_eps, lw.gu_w8, lw.gu_s, nullptr, nullptr, w.mlp, B, 2 * I, H, H, I, 0,
-                                          O3V_EPI_SWIGLU, s));
-                TRY(o3v_linear_decode_fp8(w.mlp, nullptr, 0.f, lw.down_w8, lw.down_s, nullptr, st->x, st->x, B, H, I, I, H, H,
-                                          O3V_EPI_RESIDUAL, s));
-                continue;
-            }
-            if (fp8b) {
-                TRY(o3v_rmsnorm(st->x, lw.ln2, w.h, B, H, H, H, d->rms_eps, s));
-                TRY(o3v_linear_decode_fp8_rows(w.h, lw.gu_w8p, lw.gu_s, nullptr, nullptr, w.mlp, B, 2 * I, H, H, I, 0, O3V_EPI_SWIGLU, s));
-                TRY(o3v_linear_decode_fp8_rows(w.mlp, lw.down_w8p, lw.down_s, nullptr, st->x, st->x, B, H, I, I, H, H, O3V_EPI_RESIDUAL, s));
-                continue;
-            }
-            if (norm_apart) {
-                if (!h2_ready) TRY(o3v_rmsnorm(st->x, lw.ln2, w.h, B, H, H, H, d->rms_eps, s));
-                TRY(o3v_linear_decode(w.h, nullptr, 0.f, lw.gu_w, lw.gu_wp, nullptr, nullptr, w.mlp, B, 2 * I, H, H, I, 0,
-                                      O3V_EPI_SWIGLU, s));
-                h2_ready = false;
-                if (tail) {  // down_proj + the next layer's first norm (the head's norm after the last layer)
-                    const bool last = l + 1 == d->layers;
-                    const uint32_t epoch = (uint32_t)(step * d->layers + l) * 2u + 2u;
-                    TRY(o3v_linear_decode_norm_next(w.mlp, lw.down_wp, st->x, st->x, B, H, I, I, H, H, last ? d->final_norm : d->layer[l + 1].ln1,
-                                                    d->rms_eps, last ? w.normed : w.h, H, st->sync, epoch, s));
-                    (last ? normed_ready : h_ready) = true;
-                    continue;
-                }
-            } else {
-                TRY(o3v_linear_decode(st->x, lw.ln2, d->rms_eps, lw.gu_w, lw.gu_wp, nullptr, nullptr, w.mlp, B, 2 * I, H, H, I, 0,
-                                      O3V_EPI_SWIGLU, s));
-            }
-            TRY(o3v_linear_decode(w.mlp, nullptr, 0.f, lw.down_w, lw.down_wp, nullptr, st->x, st->x, B, H, I, I, H, H,
-                                  O3V_EPI_RESIDUAL, s));
-        }
-        if (hs) {
-            ++hs[0];
-            hs[1] += o3v_tl_launches - launches0;
+        for (int l = 0; l < d->layers; ++l) TRY(c.layer(l));
+        if (c.hs) {
+            ++c.hs[0];
+            c.hs[1] += o3v_tl_launches - launches0;
         }
         // the head follows the layers: fp8 rows only when the layer stack of this call streams fp8 rows
-        TRY(llm_head(d, st->x, H, B, w.normed, st->logits, fp8 || fp8b, s, normed_ready));
+        TRY(llm_head(d, st->x, c.H, B, c.w.normed, st->logits, c.r.weights, s, c.normed_ready));
     }
     return O3V_OK;
 }

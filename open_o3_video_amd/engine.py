@@ -102,6 +102,7 @@ class O3VEngine:
         # 4.324 vs 4.321: the in-launch chain store-ack -> ticket -> poll -> row load costs the residual linear +6.4 us, the launch it
         # removes 5.9 us; profiles/r03_tail_norm_ab.txt): off unless O3V_TAIL_NORM=1
         self.tail_norm = os.environ.get("O3V_TAIL_NORM", "0") == "1"
+        self.qkv_fused_norm = os.environ.get("O3V_QKV_FUSED_NORM", "1") != "0"     # A/B switch for the norm fused into q/k/v at 8 rows
         # video rope arithmetic (indexing.rope_index): "tf5" = transformers 5.15 (goldens G5b / G14 / G15), "pinned" = the
         # libraries the reference installs (transformers @336dc69d, vllm 0.7.2).  The facades choose; images do not depend on it.
         self.position_mode = "tf5"
@@ -615,7 +616,8 @@ class O3VEngine:
                               rows_per_prompt=G if shared_prompt else 0)
         stats = (C.c_longlong * 4)(0, 0, 0, 0)      # decode forwards, launches in their layer loops, fused / stand-alone attention halves
         st.host_stats = C.cast(stats, C.c_void_p)
-        st.flags = (1 if self.layer_block else 0) | (0 if self.tail_norm else 2) | (4 if os.environ.get("O3V_QKV_FUSED_NORM", "1") == "0" else 0)
+        st.flags = ((_lib.DECODE_LAYER_BLOCK if self.layer_block else 0) | (0 if self.tail_norm else _lib.DECODE_NO_TAIL_NORM) |
+                    (0 if self.qkv_fused_norm else _lib.DECODE_NO_QKV_FUSED_NORM))
         tm["kv_cache_bytes"] = int((kc.numel() + vc.numel() + (kc0.numel() + vc0.numel() if shared_prompt else 0)) * 2)
         # ---- decode loop: chunks of steps enqueued from C++, one host check per chunk (TF:utils.py:2936-2937)
         done = 0
@@ -633,13 +635,8 @@ class O3VEngine:
         while done < T:
             # the first chunk is short whenever the one-launch block is in use: its time-out word is read right after it
             n = min(chunk if (done or sync is None) else min(chunk, getattr(self, "_first_chunk", 16)), T - done)
-            if so is not None:
-                _lib.call("o3v_llm_decode_ex", C.byref(self.w.llm), C.byref(st), None if lp_opts is None else C.byref(lp_opts),
-                          C.byref(so), done, n, int(done + n == T), _stream())
-            elif lp_opts is None:
-                _lib.call("o3v_llm_decode", C.byref(self.w.llm), C.byref(st), done, n, int(done + n == T), _stream())
-            else:
-                _lib.call("o3v_llm_decode_lp", C.byref(self.w.llm), C.byref(st), C.byref(lp_opts), done, n, int(done + n == T), _stream())
+            _lib.call("o3v_llm_decode_ex", C.byref(self.w.llm), C.byref(st), None if lp_opts is None else C.byref(lp_opts),
+                      None if so is None else C.byref(so), done, n, int(done + n == T), _stream())
             first = done == 0
             done += n
             if first and done < T:
