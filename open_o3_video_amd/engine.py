@@ -14,7 +14,7 @@ import ctypes as C
 import math
 import os
 from dataclasses import dataclass
-from typing import Optional, Sequence
+from typing import NamedTuple, Optional, Sequence
 
 import numpy as np
 import torch
@@ -35,6 +35,98 @@ def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+def prompt_arrays(input_ids, attention_mask=None, check_left_padding: bool = True):
+    """Prompt ids and mask (tensor, array or list; one row may come 1-D) -> (ids i64 [B0, S], mask i64 [B0, S], pad i64 [B0]:
+    masked slots per row).  A missing mask is all ones."""
+    as_np = lambda a: np.asarray(a.cpu() if torch.is_tensor(a) else a, dtype=np.int64)
+    ids = as_np(input_ids)
+    if ids.ndim == 1:
+        ids = ids[None]
+    mask = np.ones_like(ids) if attention_mask is None else as_np(attention_mask)
+    if mask.ndim == 1:
+        mask = mask[None]
+    pad = (mask == 0).sum(axis=1)
+    if check_left_padding and not all((mask[b, pad[b]:] == 1).all() for b in range(ids.shape[0])):
+        raise ValueError("only left padding is supported (padding_side='left', R:grpo_trainer.py:546)")
+    return ids, mask, pad
+
+
+def visual_identity(pixel_values, grid, frames, vis_embeds, pixel_values_videos, vgrid, video_frames):
+    """The visual inputs of a prompt as the named tensors O3VEngine._prompt_key checksums: the group generate stores the hand-over
+    under this identity and completion_logps looks it up, so both sides name them here."""
+    return (("pv", pixel_values), ("grid", grid), ("frames", frames), ("vis", vis_embeds), ("pvv", pixel_values_videos),
+            ("vgrid", vgrid), ("vframes", video_frames))
+
+
+class DecodePlan(NamedTuple):
+    """What one generate call decides about its decode before any buffer exists (plan_decode)."""
+    B: int                  # decode rows: B0 prompts x G completions
+    own_splits: int         # 128-key chunks of a row's generated tokens
+    shared_prompt: bool     # the prompt's K/V is kept once per prompt (kc0 / vc0); the rows' caches hold only generated tokens
+    Tmax: int               # slots per row of the decode caches
+    nsplit: int             # o3v_decode_state.nsplit: context splits of the decode attention, negative = shared-read group kernel
+    group: int              # o3v_decode_state.group: rows per shared-prefix (sub-)group, 0 = independent rows
+    want_sync: bool         # the ticket / mailbox buffer of the in-launch hand-offs exists
+
+
+def plan_decode(num_attention_heads: int, num_key_value_heads: int, head_dim: int, B0: int, G: int, S: int, T: int,
+                group_attention: bool = True, group_attention_mode: str = "auto", fused: bool = True, tail_norm: bool = False,
+                nsplit_override: Optional[int] = None) -> DecodePlan:
+    """The decode attention plan of a generate call: B0 prompts of S slots, G completions each, T new tokens.  Pure arithmetic on
+    the model's head geometry and the engine's switches (`fused`: the one-launch decode forms are allowed in this call;
+    `nsplit_override`: the O3V_NSPLIT A/B switch)."""
+    B = B0 * G
+    # G completions of a prompt share its K/V (head_dim 128, own keys in <= 32 splits): the prompt's K/V is kept ONCE
+    # (kc0 / vc0) and every row's cache holds only its generated tokens -- no G-fold copy of the prompt
+    own_splits = (T + 127) // 128
+    shared_prompt = G > 1 and head_dim == 128 and own_splits <= 32 and group_attention
+    Tmax = T if shared_prompt else S + T
+    # context splits of the decode attention: one 128-key chunk per block at 1-4 rows; from 8 rows on fewer, longer chunks
+    # so that the grid stays near 640 blocks (measured, 7B: 8 rows 40 -> 20 splits 3.85 -> 3.72 ms/step; 16 independent rows
+    # 32 -> 8 splits 2020 -> 2128 tok/s; 2 and 4 rows are best at 40)
+    nsplit = max(1, min(64, (S + T + 127) // 128, max(1, 640 // max(1, B * num_key_value_heads))))
+    if nsplit_override is not None:
+        nsplit = nsplit_override
+    # G completions of a prompt share its K/V: the group kernel reads the prompt keys once per group (head_dim 128,
+    # G * n_rep <= 64 query rows per kv head, prefix splits + own-key splits <= 64)
+    n_rep = num_attention_heads // num_key_value_heads
+    group = G if shared_prompt else 0
+    mode = group_attention_mode
+    if group:
+        # the one-pass kernel holds a sub-group's query rows as MFMA columns (<= 64); sub-groups of 4 rows measured best
+        sub = max(d for d in range(1, G + 1) if G % d == 0 and d <= 4 and d * n_rep <= 64)
+        if mode == "auto":
+            # measured, 7B dims, ms per decode step (tools/measure_configs.py rollout / rollout_eval), per-row kernel reading
+            # the leader's prefix through the shared L2 | one-pass kernel in sub-groups of 4 (prefix + own keys, one launch):
+            #   S=4.5k: G=4 3.45 | 3.53   G=8 3.71 | 3.79   G=12 4.06 | 4.09   G=16 4.42 | 4.36
+            #   S=10k : G=8 4.37 | 3.97
+            mode = "kernel" if (S >= 8192 or B >= 16) and sub > 1 else "shared_read"
+        if mode == "kernel" and sub > 1:
+            group = sub
+            # prefix splits: ~320 blocks in all (measured: G=16, S=4.5k 36 -> 18 splits 4.80 -> 4.63 ms/step; G=8, S=10k is
+            # best left at its 63)
+            nsplit = max(1, min(64 - own_splits, (S + 127) // 128, max(1, 320 // (num_key_value_heads * (B // sub)))))
+            if S >= 8192:
+                nsplit = max(1, min(64 - own_splits, (S + 127) // 128))
+        else:
+            nsplit = -nsplit
+    # tickets / mailboxes of the one-launch attention block (batch 1); 8..32 rows: the residual linears of the batched decode
+    # normalise for the next linear through the same buffer
+    want_sync = bool(fused and (B == 1 or (B >= 8 and tail_norm)))
+    return DecodePlan(B, own_splits, bool(shared_prompt), Tmax, nsplit, group, want_sync)
+
+
+def trimmed_length(gen: np.ndarray, eos_ids, ended: dict, done: int) -> int:
+    """Columns of gen i64 [B, done] that HF would have produced: up to and including the step at which the last row finished.
+    A row finishes at its first id of `eos_ids`, a row the stop checker ended (`ended`: row -> tokens it keeps) at the column the
+    checker named if that comes first, any other row at `done`; at least one column stays."""
+    hit = np.isin(gen, list(eos_ids))
+    fin_at = np.where(hit.any(axis=1), hit.argmax(axis=1) + 1, done)
+    for b, end in ended.items():
+        fin_at[b] = min(fin_at[b], end)
+    return int(max(1, min(done, fin_at.max())))
+
+
 @dataclass
 class Logprobs:
     """Top-N log-probs of a run of positions (vLLM SamplingParams.logprobs / prompt_logprobs; o3v_logprob_opts in include/o3v.h)."""
@@ -42,6 +134,13 @@ class Logprobs:
     rank: torch.Tensor                 # i32 [B, T]: 1 + tokens with a strictly larger log-prob
     top_ids: torch.Tensor              # i32 [B, T, N]: descending log-prob, ties to the lower id
     top: torch.Tensor                  # f32 [B, T, N]
+
+    @classmethod
+    def zeros(cls, B: int, T: int, n: int, device) -> "Logprobs":
+        return cls(token=torch.zeros((B, T), dtype=torch.float32, device=device),
+                   rank=torch.zeros((B, T), dtype=torch.int32, device=device),
+                   top_ids=torch.zeros((B, T, n), dtype=torch.int32, device=device),
+                   top=torch.zeros((B, T, n), dtype=torch.float32, device=device))
 
 
 @dataclass
@@ -55,6 +154,80 @@ class GenerateOutput:
     # generate(prompt_logprobs=N): [B0, S-1(, N)] per prompt, column j = prompt token j+1 given the tokens before it (left-padded
     # rows: the columns before the row's first real token carry no meaning)
     prompt_logprobs: Optional[Logprobs] = None
+
+
+class _DecodeBuffers:
+    """The device state of one generate call's decode: every tensor whose address goes into o3v_decode_state / o3v_sampling_opts /
+    o3v_logprob_opts, the structs themselves (st; so / lp_opts: None when the call does not use them) and the host_stats array.
+    The structs hold bare addresses, so this object lives until the last o3v_llm_decode_ex call and the final check_waits()."""
+
+    def __init__(self, eng: "O3VEngine", plan: DecodePlan, S, T, G, ids_rep, pad_rep, eos_token_ids, row_ids, return_margins, n_lp,
+                 sampling, knobs, cosd, sind, logits, kc, vc, kc0, vc0):
+        tc, dev = eng.cfg.text, eng.dev
+        B, V = plan.B, tc.vocab_size
+        zeros = lambda shape, dtype: torch.zeros(shape, dtype=dtype, device=dev)
+        empty = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=dev)
+        addr = lambda t: 0 if t is None else t.data_ptr()
+        self.caches, self.tables, self.logits = (kc, vc, kc0, vc0), (cosd, sind), logits
+        self.seen = zeros((B, V), torch.uint8)
+        if knobs["rep_penalty"] != 1.0:
+            ids_dev = torch.from_numpy(ids_rep.astype(np.int32)).to(dev)
+            _lib.call("o3v_mark_seen", _ptr(ids_dev), _ptr(self.seen), B, S, V, _stream())
+        self.cur_tok, self.finished = zeros(B, torch.int32), zeros(B, torch.int32)
+        self.out_ids = torch.full((B, T), knobs["pad_id"], dtype=torch.int32, device=dev)
+        self.margins = zeros((B, T), torch.float32) if return_margins else None
+        self.eos = torch.tensor(list(eos_token_ids) or [0], dtype=torch.int32, device=dev)
+        self.k_lo = torch.from_numpy(pad_rep.astype(np.int32)).to(dev)
+        self.rid = torch.tensor(list(row_ids) if row_ids is not None else list(range(B)), dtype=torch.int32, device=dev)
+        n_rep_total = B * tc.num_attention_heads
+        self.part_o = empty(n_rep_total * 64 * tc.head_dim, torch.float32)
+        self.part_ml = empty(n_rep_total * 64 * 2, torch.float32)
+        self.scratch = empty((B, _lib.SAMPLE_SCRATCH_FLOATS if knobs["do_sample"] or n_lp or sampling else 256), torch.float32)
+        self.so = None
+        if sampling:    # the extended sampler kernels: static-edit vectors and (penalties only) the u16 output counts
+            self.bias, self.early = (None if v is None else torch.from_numpy(v).to(dev)
+                                     for v in (sampling["bias"], sampling["bias_early"]))
+            self.counts = zeros((B, V), torch.int16) if sampling["counts"] else None
+            self.so = _lib.SamplingOpts(min_p=sampling["min_p"], presence=sampling["presence"], frequency=sampling["frequency"],
+                                        min_tokens=sampling["min_tokens"], bias=addr(self.bias), bias_early=addr(self.early),
+                                        out_counts=addr(self.counts))
+        self.lp = self.lp_opts = None
+        if n_lp:
+            lp = self.lp = Logprobs.zeros(B, T, n_lp, dev)
+            self.lp_opts = _lib.LogprobOpts(n=n_lp, chosen_lp=lp.token.data_ptr(), chosen_rank=lp.rank.data_ptr(),
+                                            top_ids=lp.top_ids.data_ptr(), top_lp=lp.top.data_ptr())
+        self.x = empty((B, tc.hidden_size), torch.bfloat16)
+        nbytes = _lib.load().o3v_llm_workspace_bytes(C.byref(eng.w.llm), B)
+        self.ws = empty(nbytes, torch.uint8)
+        # tickets / mailboxes of the in-launch hand-offs: zeroed once per call, epochs count the launches
+        self.sync = None
+        if plan.want_sync:
+            self.sync = zeros(_lib.load().o3v_decode_sync_bytes(), torch.uint8)
+            if getattr(eng, "_debug_poison_sync", False):     # test hook: tickets that can never reach "last" -> the waits give up
+                self.sync[:1024].view(torch.int32).fill_(0x40000000)
+        shared = plan.shared_prompt
+        self.st = _lib.DecodeState(B=B, S=S, Tmax=plan.Tmax, Tnew=T, nsplit=plan.nsplit, x=self.x.data_ptr(), kcache=kc.data_ptr(),
+                                   vcache=vc.data_ptr(), cosT=cosd.data_ptr(), sinT=sind.data_ptr(), logits=logits.data_ptr(),
+                                   seen=self.seen.data_ptr(), cur_tok=self.cur_tok.data_ptr(), finished=self.finished.data_ptr(),
+                                   out_ids=self.out_ids.data_ptr(), margins=addr(self.margins), eos_ids=self.eos.data_ptr(),
+                                   k_lo=self.k_lo.data_ptr(), row_id=self.rid.data_ptr(), part_o=self.part_o.data_ptr(),
+                                   part_ml=self.part_ml.data_ptr(), sample_scratch=self.scratch.data_ptr(),
+                                   workspace=self.ws.data_ptr(), ws_bytes=nbytes, group=plan.group, sync=addr(self.sync),
+                                   kprefix=kc0.data_ptr() if shared else 0, vprefix=vc0.data_ptr() if shared else 0,
+                                   prefix_cap=S if shared else 0, rows_per_prompt=G if shared else 0, **knobs)
+        # decode forwards, launches in their layer loops, fused / stand-alone attention halves
+        self.host_stats = (C.c_longlong * 4)(0, 0, 0, 0)
+        self.st.host_stats = C.cast(self.host_stats, C.c_void_p)
+        self.st.flags = ((_lib.DECODE_LAYER_BLOCK if eng.layer_block else 0) | (0 if eng.tail_norm else _lib.DECODE_NO_TAIL_NORM) |
+                         (0 if eng.qkv_fused_norm else _lib.DECODE_NO_QKV_FUSED_NORM))
+
+    def check_waits(self):
+        """Reads the sticky time-out word of the in-launch waits (a device-to-host copy); raises if one of them gave up."""
+        if self.sync is None:
+            return
+        code = int(self.sync[_lib.SYNC_TMO_BYTE:_lib.SYNC_TMO_BYTE + 4].view(torch.int32)[0].item())
+        if code:
+            raise O3VEngine._InLaunchWaitGaveUp(f"decode: an in-launch wait gave up (code {code:#x})")
 
 
 class O3VEngine:
@@ -175,6 +348,11 @@ class O3VEngine:
         _lib.call("o3v_cast_pad_f32_bf16", _ptr(pv), _ptr(out), pv.shape[0], pv.shape[1], vc.patch_k_pad, _stream())
         return out
 
+    def frames_grid(self, frames: torch.Tensor) -> np.ndarray:
+        """grid_thw [T,3] of frames-as-images [T,3,H,W]: every frame is its own image of one temporal patch."""
+        ps = self.cfg.vision.patch_size
+        return np.asarray([[1, frames.shape[2] // ps, frames.shape[3] // ps]] * frames.shape[0], dtype=np.int64)
+
     def pixels_from_frames(self, frames: torch.Tensor):
         """frames [T,3,H,W] uint8 or f32 (0..255, H,W multiples of 28) -> (bf16 [P,Kp], grid_thw [T,3])."""
         vc = self.cfg.vision
@@ -190,8 +368,7 @@ class O3VEngine:
         out = torch.empty((P, vc.patch_k_pad), dtype=torch.bfloat16, device=self.dev)
         _lib.call("o3v_patchify_ps", _ptr(fr), int(is_u8), _ptr(out), T, H, W, vc.patch_k_pad, ps, self.clip_mean, self.clip_std,
                   _stream())
-        grid = np.asarray([[1, H // ps, W // ps]] * T, dtype=np.int64)
-        return out, grid
+        return out, self.frames_grid(frames)
 
     def pixels_from_video(self, frames: torch.Tensor):
         """ONE native video [T,3,H,W] uint8 or f32 (0..255) -> (bf16 [ceil(T/2)*gh*gw, Kp], grid [[ceil(T/2), gh, gw]]): temporal
@@ -437,18 +614,10 @@ class O3VEngine:
         tokens.  Such a row emits pad from the next step on, what it emitted past n is replaced by pad, and the trailing-pad trim
         counts it as finished at n."""
         cfg, tc = self.cfg, self.cfg.text
-        ids = np.asarray(input_ids.cpu() if torch.is_tensor(input_ids) else input_ids, dtype=np.int64)
-        if ids.ndim == 1:
-            ids = ids[None]
+        ids, mask, pad = prompt_arrays(input_ids, attention_mask)
         B0, S = ids.shape
-        mask = np.ones_like(ids) if attention_mask is None else np.asarray(
-            attention_mask.cpu() if torch.is_tensor(attention_mask) else attention_mask, dtype=np.int64)
-        pad = (mask == 0).sum(axis=1)
-        if not all((mask[b, pad[b]:] == 1).all() for b in range(B0)):
-            raise ValueError("only left padding is supported (padding_side='left', R:grpo_trainer.py:546)")
         G = int(num_return_sequences)
-        B = B0 * G
-        if B > self.MAX_ROWS:
+        if B0 * G > self.MAX_ROWS:
             raise ValueError(f"at most {self.MAX_ROWS} sequences per engine call (two 16-column MFMA blocks in the decode linears); "
                              "shard larger batches")
         pad_id = cfg.pad_token_id if pad_token_id is None else int(pad_token_id)
@@ -459,9 +628,13 @@ class O3VEngine:
         for what, v in (("logprobs", n_lp), ("prompt_logprobs", n_plp)):
             if not 0 <= v <= _lib.MAX_LOGPROBS:
                 raise ValueError(f"`{what}` must be in 0..{_lib.MAX_LOGPROBS}, got {v}")
-        V_ = tc.vocab_size
-        sampling = self._sampling_vectors(V_, T, eos_token_ids, bool(do_sample), min_p, presence_penalty, frequency_penalty,
+        sampling = self._sampling_vectors(tc.vocab_size, T, eos_token_ids, bool(do_sample), min_p, presence_penalty, frequency_penalty,
                                           min_new_tokens, token_bias, allowed_token_ids, banned_token_ids)
+        nsplit_env = os.environ.get("O3V_NSPLIT")      # A/B switch (tools/probes), read at every call
+        plan = plan_decode(tc.num_attention_heads, tc.num_key_value_heads, tc.head_dim, B0, G, S, T, self.group_attention,
+                           self.group_attention_mode, self.fused_decode and _fused_ok, self.tail_norm,
+                           int(nsplit_env) if nsplit_env else None)
+        B = plan.B
         tm = {}
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)] if sync_timings else None
 
@@ -475,17 +648,70 @@ class O3VEngine:
         vis, grid, vgrid, n_img_rows = self._visual(pixel_values, image_grid_thw, frames, vis_embeds, pixel_values_videos, video_grid_thw,
                                                     video_frames)
         mark(1)
-        # ---- positions + prefill (once per prompt)
+        # ---- positions + prefill (once per prompt); a call asking for prompt log-probs neither reuses nor stores prefix K/V
         pos, deltas = self._positions(ids, mask, grid, vgrid, second_per_grid_ts)
-        # G completions of a prompt share its K/V (head_dim 128, own keys in <= 32 splits): the prompt's K/V is kept ONCE
-        # (kc0 / vc0) and every row's cache holds only its generated tokens -- no G-fold copy of the prompt
-        own_splits = (T + 127) // 128
-        shared_prompt = G > 1 and tc.head_dim == 128 and own_splits <= 32 and self.group_attention
-        Tmax = T if shared_prompt else S + T
-        kc, vc = self.alloc_cache(B, Tmax)
+        x, kc, vc, kc0, vc0, past = self._prefill_prompt(ids, pad, pos, vis, n_img_rows, G, plan, None if n_plp else prefix_key)
+        tm["prefix_tokens_reused"] = past
+        self._last_prompt = None
+        if self.reuse_prompt_kv and plan.shared_prompt and B0 == 1:
+            key = self._prompt_key(ids, mask, pos, visual_identity(pixel_values, grid, frames, vis_embeds, pixel_values_videos, vgrid,
+                                                                   video_frames))
+            self._last_prompt = {"key": key, "kc0": kc0, "vc0": vc0, "x_last": x.view(B0, S - past, -1)[0, -1:, :].clone(),
+                                 "deltas": np.array(deltas, copy=True)}
+        plp = self._prompt_logprobs(x.view(B0, S, -1), ids, n_plp) if n_plp else None
+        last = x.view(B0, S - past, -1)[:, -1, :]               # left padding: every row ends at S-1
+        logits0 = self.head(last)                               # [B0, V]
+        logits = logits0.repeat_interleave(G, dim=0).contiguous() if G > 1 else logits0
+        mark(2)
+        # ---- decode state
+        dpos = indexing.decode_positions(mask, deltas, T)       # [3,B0,T]
+        if G > 1:
+            dpos = np.repeat(dpos, G, axis=1)
+        cosd, sind = self.mrope_table(dpos.reshape(3, B * T))
+        ids_rep = np.repeat(ids, G, axis=0) if G > 1 else ids
+        knobs = dict(pad_id=pad_id, n_eos=len(eos_token_ids), do_sample=int(do_sample), rep_penalty=float(repetition_penalty),
+                     temperature=float(temperature), top_p=float(top_p), seed=int(seed) & (2 ** 64 - 1), top_k=max(0, int(top_k or 0)))
+        buf = _DecodeBuffers(self, plan, S, T, G, ids_rep, np.repeat(pad, G) if G > 1 else pad, eos_token_ids, row_ids, return_margins,
+                             n_lp, sampling, knobs, cosd, sind, logits, kc, vc, kc0, vc0)
+        tm["kv_cache_bytes"] = int((kc.numel() + vc.numel() + (kc0.numel() + vc0.numel() if plan.shared_prompt else 0)) * 2)
+        use_eos = len(eos_token_ids) > 0
+        done, ended = self._decode_loop(buf, T, use_eos, steps_per_sync, stop_checker)
+        mark(3)
+        stats = buf.host_stats
+        layers_run = stats[0] * tc.num_hidden_layers
+        tm["decode_forwards"] = int(stats[0])
+        tm["launches_per_layer"] = (stats[1] / layers_run) if layers_run else None
+        tm["fused_attention_layers"], tm["standalone_attention_layers"] = int(stats[2]), int(stats[3])
+        buf.check_waits()
+        if getattr(self, "_debug_keep", False):     # probe hook: the decode's state after the last step
+            self._debug_last = {"kc": kc, "vc": vc, "logits": logits, "x": buf.x, "S": S, "cos": cosd, "sin": sind, "k_lo": buf.k_lo,
+                                "nsplit": plan.nsplit, "Tmax": plan.Tmax, "out_ids": buf.out_ids}
+        gen = buf.out_ids[:, :done].to(torch.int64)
+        if use_eos or ended:
+            # HF stops at the step where every row has finished: trim trailing all-pad columns generated past it
+            done = trimmed_length(gen.cpu().numpy(), eos_token_ids, ended, done)
+            gen = gen[:, :done]
+        seqs = torch.cat([torch.from_numpy(ids_rep).to(self.dev), gen], dim=1)
+        if ev is not None:
+            torch.cuda.synchronize()
+            tm.update({"vit_ms": ev[0].elapsed_time(ev[1]), "prefill_ms": ev[1].elapsed_time(ev[2]),
+                       "decode_ms": ev[2].elapsed_time(ev[3])})
+        lp, margins = buf.lp, buf.margins
+        if lp is not None:
+            lp = Logprobs(lp.token[:, :done], lp.rank[:, :done], lp.top_ids[:, :done], lp.top[:, :done])
+        return GenerateOutput(sequences=seqs, margins=None if margins is None else margins[:, :done], n_steps=done,
+                              timings=tm, logprobs=lp, prompt_logprobs=plp)
+
+    def _prefill_prompt(self, ids, pad, pos, vis, n_img_rows, G, plan: DecodePlan, prefix_key):
+        """The prompt stage of generate: the caches, the tokens whose K/V are kept under `prefix_key` (single un-padded prompt)
+        copied in, the prefill of the rest, the fan-out to the G rows of each prompt, the prefix store.
+        -> (x: last-layer rows of the tokens run [B0 * (S - past), H], kc, vc: the decode caches, kc0, vc0: the prompt's K/V kept
+        once (None unless plan.shared_prompt), past: tokens reused)."""
+        B0, S = ids.shape
+        kc, vc = self.alloc_cache(plan.B, plan.Tmax)
         kc0 = vc0 = None
         past = 0
-        use_prefix = prefix_key is not None and B0 == 1 and int(pad[0]) == 0 and n_plp == 0
+        use_prefix = prefix_key is not None and B0 == 1 and int(pad[0]) == 0
         if use_prefix:
             past = self._prefix_lookup(prefix_key, ids[0])
         x = self.embed(ids, vis, first=past, n_image_rows=n_img_rows)
@@ -499,7 +725,7 @@ class O3VEngine:
                 kc0[:, :, :, :past].copy_(ent["k"][:, :, :, :past])
                 vc0[:, :, :, :past].copy_(ent["v"][:, :, :, :past])
             self.prefill(x, pos[:, :, past:], pad, B0, S - past, kc0, vc0, past=past, deepstack=ds)
-            if not shared_prompt:
+            if not plan.shared_prompt:
                 # KV fan-out: completion g of prompt b is row b*G+g (repeat_interleave order, R:grpo_trainer.py:586)
                 # (a broadcast copy into the [layers, B0, G, ...] view of the caches: no G-times temporary)
                 shp = (kc.shape[0], B0, G) + tuple(kc.shape[2:])
@@ -507,189 +733,39 @@ class O3VEngine:
                 vc.view(shp)[:, :, :, :, :S].copy_(vc0[:, :, None])
             if use_prefix:
                 self._prefix_store(prefix_key, ids[0], kc0, vc0)
-            if not shared_prompt:
+            if not plan.shared_prompt:
                 kc0 = vc0 = None
-        tm["prefix_tokens_reused"] = past
-        self._last_prompt = None
-        if self.reuse_prompt_kv and shared_prompt and B0 == 1:
-            key = self._prompt_key(ids, mask, pos, (("pv", pixel_values), ("grid", grid), ("frames", frames), ("vis", vis_embeds),
-                                                    ("pvv", pixel_values_videos), ("vgrid", vgrid), ("vframes", video_frames)))
-            self._last_prompt = {"key": key, "kc0": kc0, "vc0": vc0, "x_last": x.view(B0, S - past, -1)[0, -1:, :].clone(),
-                                 "deltas": np.array(deltas, copy=True)}
-        plp = self._prompt_logprobs(x.view(B0, S, -1), ids, n_plp) if n_plp else None
-        last = x.view(B0, S - past, -1)[:, -1, :]               # left padding: every row ends at S-1
-        logits0 = self.head(last)                               # [B0, V]
-        logits = logits0.repeat_interleave(G, dim=0).contiguous() if G > 1 else logits0
-        mark(2)
-        # ---- decode state
-        V, H = tc.vocab_size, tc.hidden_size
-        dpos = indexing.decode_positions(mask, deltas, T)       # [3,B0,T]
-        if G > 1:
-            dpos = np.repeat(dpos, G, axis=1)
-        cosd, sind = self.mrope_table(dpos.reshape(3, B * T))
-        seen = torch.zeros((B, V), dtype=torch.uint8, device=self.dev)
-        ids_rep = np.repeat(ids, G, axis=0) if G > 1 else ids
-        pad_rep = np.repeat(pad, G) if G > 1 else pad
-        if repetition_penalty != 1.0:
-            ids_dev = torch.from_numpy(ids_rep.astype(np.int32)).to(self.dev)
-            _lib.call("o3v_mark_seen", _ptr(ids_dev), _ptr(seen), B, S, V, _stream())
-        cur_tok = torch.zeros(B, dtype=torch.int32, device=self.dev)
-        finished = torch.zeros(B, dtype=torch.int32, device=self.dev)
-        out_ids = torch.full((B, T), pad_id, dtype=torch.int32, device=self.dev)
-        margins = torch.zeros((B, T), dtype=torch.float32, device=self.dev) if return_margins else None
-        eos = torch.tensor(list(eos_token_ids) or [0], dtype=torch.int32, device=self.dev)
-        k_lo = torch.from_numpy(pad_rep.astype(np.int32)).to(self.dev)
-        rid = torch.tensor(list(row_ids) if row_ids is not None else list(range(B)), dtype=torch.int32, device=self.dev)
-        n_rep_total = B * tc.num_attention_heads
-        # context splits of the decode attention: one 128-key chunk per block at 1-4 rows; from 8 rows on fewer, longer chunks
-        # so that the grid stays near 640 blocks (measured, 7B: 8 rows 40 -> 20 splits 3.85 -> 3.72 ms/step; 16 independent rows
-        # 32 -> 8 splits 2020 -> 2128 tok/s; 2 and 4 rows are best at 40)
-        nsplit = max(1, min(64, (S + T + 127) // 128, max(1, 640 // max(1, B * tc.num_key_value_heads))))
-        if os.environ.get("O3V_NSPLIT"):      # A/B switch (tools/probes)
-            nsplit = int(os.environ["O3V_NSPLIT"])
-        # G completions of a prompt share its K/V: the group kernel reads the prompt keys once per group (head_dim 128,
-        # G * n_rep <= 64 query rows per kv head, prefix splits + own-key splits <= 64)
-        n_rep = tc.num_attention_heads // tc.num_key_value_heads
-        group = G if shared_prompt else 0
-        mode = self.group_attention_mode
-        if group:
-            # the one-pass kernel holds a sub-group's query rows as MFMA columns (<= 64); sub-groups of 4 rows measured best
-            sub = max(d for d in range(1, G + 1) if G % d == 0 and d <= 4 and d * n_rep <= 64)
-            if mode == "auto":
-                # measured, 7B dims, ms per decode step (tools/measure_configs.py rollout / rollout_eval), per-row kernel reading
-                # the leader's prefix through the shared L2 | one-pass kernel in sub-groups of 4 (prefix + own keys, one launch):
-                #   S=4.5k: G=4 3.45 | 3.53   G=8 3.71 | 3.79   G=12 4.06 | 4.09   G=16 4.42 | 4.36
-                #   S=10k : G=8 4.37 | 3.97
-                mode = "kernel" if (S >= 8192 or B >= 16) and sub > 1 else "shared_read"
-            if mode == "kernel" and sub > 1:
-                group = sub
-                # prefix splits: ~320 blocks in all (measured: G=16, S=4.5k 36 -> 18 splits 4.80 -> 4.63 ms/step; G=8, S=10k is
-                # best left at its 63)
-                nsplit = max(1, min(64 - own_splits, (S + 127) // 128, max(1, 320 // (tc.num_key_value_heads * (B // sub)))))
-                if S >= 8192:
-                    nsplit = max(1, min(64 - own_splits, (S + 127) // 128))
-            else:
-                nsplit = -nsplit
-        part_o = torch.empty(n_rep_total * 64 * tc.head_dim, dtype=torch.float32, device=self.dev)
-        part_ml = torch.empty(n_rep_total * 64 * 2, dtype=torch.float32, device=self.dev)
-        scratch = torch.empty((B, _lib.SAMPLE_SCRATCH_FLOATS if do_sample or n_lp or sampling else 256), dtype=torch.float32,
-                              device=self.dev)
-        so = so_keep = None
-        if sampling:    # the extended sampler kernels: static-edit vectors and (penalties only) the u16 output counts
-            bias, early = (None if v is None else torch.from_numpy(v).to(self.dev) for v in (sampling["bias"], sampling["bias_early"]))
-            counts = torch.zeros((B, V_), dtype=torch.int16, device=self.dev) if sampling["counts"] else None
-            so_keep = (bias, early, counts)
-            so = _lib.SamplingOpts(min_p=sampling["min_p"], presence=sampling["presence"], frequency=sampling["frequency"],
-                                   min_tokens=sampling["min_tokens"], bias=0 if bias is None else bias.data_ptr(),
-                                   bias_early=0 if early is None else early.data_ptr(),
-                                   out_counts=0 if counts is None else counts.data_ptr())
-        lp = lp_opts = None
-        if n_lp:
-            lp = Logprobs(token=torch.zeros((B, T), dtype=torch.float32, device=self.dev),
-                          rank=torch.zeros((B, T), dtype=torch.int32, device=self.dev),
-                          top_ids=torch.zeros((B, T, n_lp), dtype=torch.int32, device=self.dev),
-                          top=torch.zeros((B, T, n_lp), dtype=torch.float32, device=self.dev))
-            lp_opts = _lib.LogprobOpts(n=n_lp, chosen_lp=lp.token.data_ptr(), chosen_rank=lp.rank.data_ptr(),
-                                       top_ids=lp.top_ids.data_ptr(), top_lp=lp.top.data_ptr())
-        xdec = torch.empty((B, H), dtype=torch.bfloat16, device=self.dev)
-        nbytes = _lib.load().o3v_llm_workspace_bytes(C.byref(self.w.llm), B)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
-        # tickets / mailboxes of the one-launch attention block (batch 1): zeroed once per call, epochs count the launches
-        sync = None
-        # (8..32 rows: the residual linears of the batched decode normalise for the next linear through the same buffer)
-        if self.fused_decode and _fused_ok and (B == 1 or (B >= 8 and self.tail_norm)):
-            sync = torch.zeros(_lib.load().o3v_decode_sync_bytes(), dtype=torch.uint8, device=self.dev)
-            if getattr(self, "_debug_poison_sync", False):     # test hook: tickets that can never reach "last" -> the waits give up
-                sync[:1024].view(torch.int32).fill_(0x40000000)
-        st = _lib.DecodeState(B=B, S=S, Tmax=Tmax, Tnew=T, nsplit=nsplit, pad_id=pad_id, n_eos=len(eos_token_ids),
-                              do_sample=int(do_sample), rep_penalty=float(repetition_penalty), temperature=float(temperature),
-                              top_p=float(top_p), seed=int(seed) & (2 ** 64 - 1), x=xdec.data_ptr(), kcache=kc.data_ptr(),
-                              vcache=vc.data_ptr(), cosT=cosd.data_ptr(), sinT=sind.data_ptr(), logits=logits.data_ptr(),
-                              seen=seen.data_ptr(), cur_tok=cur_tok.data_ptr(), finished=finished.data_ptr(),
-                              out_ids=out_ids.data_ptr(), margins=0 if margins is None else margins.data_ptr(),
-                              eos_ids=eos.data_ptr(), k_lo=k_lo.data_ptr(), row_id=rid.data_ptr(),
-                              part_o=part_o.data_ptr(), part_ml=part_ml.data_ptr(),
-                              sample_scratch=scratch.data_ptr(), workspace=ws.data_ptr(),
-                              ws_bytes=nbytes, group=group, sync=0 if sync is None else sync.data_ptr(),
-                              top_k=max(0, int(top_k or 0)), kprefix=kc0.data_ptr() if shared_prompt else 0,
-                              vprefix=vc0.data_ptr() if shared_prompt else 0, prefix_cap=S if shared_prompt else 0,
-                              rows_per_prompt=G if shared_prompt else 0)
-        stats = (C.c_longlong * 4)(0, 0, 0, 0)      # decode forwards, launches in their layer loops, fused / stand-alone attention halves
-        st.host_stats = C.cast(stats, C.c_void_p)
-        st.flags = ((_lib.DECODE_LAYER_BLOCK if self.layer_block else 0) | (0 if self.tail_norm else _lib.DECODE_NO_TAIL_NORM) |
-                    (0 if self.qkv_fused_norm else _lib.DECODE_NO_QKV_FUSED_NORM))
-        tm["kv_cache_bytes"] = int((kc.numel() + vc.numel() + (kc0.numel() + vc0.numel() if shared_prompt else 0)) * 2)
-        # ---- decode loop: chunks of steps enqueued from C++, one host check per chunk (TF:utils.py:2936-2937)
+        return x, kc, vc, kc0, vc0, past
+
+    def _decode_loop(self, buf: "_DecodeBuffers", T: int, use_eos: bool, steps_per_sync: int, stop_checker):
+        """Chunks of decode steps enqueued from C++, one host check per chunk (TF:utils.py:2936-2937) -> (steps done, ended: rows
+        the stop checker ended -> number of tokens they keep)."""
+        B, pad_id = buf.st.B, buf.st.pad_id
+        lp_opts, so = (None if o is None else C.byref(o) for o in (buf.lp_opts, buf.so))
         done = 0
-        use_eos = len(eos_token_ids) > 0
         chunk = max(1, int(steps_per_sync)) if (use_eos or stop_checker is not None) else T
-        ended = {}      # rows the stop checker ended -> number of tokens they keep
-
-        def check_waits():
-            if sync is None:
-                return
-            code = int(sync[_lib.SYNC_TMO_BYTE:_lib.SYNC_TMO_BYTE + 4].view(torch.int32)[0].item())
-            if code:
-                raise O3VEngine._InLaunchWaitGaveUp(f"decode: an in-launch wait gave up (code {code:#x})")
-
+        ended = {}
         while done < T:
             # the first chunk is short whenever the one-launch block is in use: its time-out word is read right after it
-            n = min(chunk if (done or sync is None) else min(chunk, getattr(self, "_first_chunk", 16)), T - done)
-            _lib.call("o3v_llm_decode_ex", C.byref(self.w.llm), C.byref(st), None if lp_opts is None else C.byref(lp_opts),
-                      None if so is None else C.byref(so), done, n, int(done + n == T), _stream())
+            n = min(chunk if (done or buf.sync is None) else min(chunk, getattr(self, "_first_chunk", 16)), T - done)
+            _lib.call("o3v_llm_decode_ex", C.byref(self.w.llm), C.byref(buf.st), lp_opts, so, done, n, int(done + n == T), _stream())
             first = done == 0
             done += n
             if first and done < T:
-                check_waits()
+                buf.check_waits()
             if stop_checker is not None:
-                hits = stop_checker(out_ids[:, :done].to(torch.int64).cpu())
+                hits = stop_checker(buf.out_ids[:, :done].to(torch.int64).cpu())
                 for b, end in (hits.items() if hasattr(hits, "items") else (hits or ())):
                     b, end = int(b), int(end)
                     if not (0 <= b < B and 0 <= end <= done):
                         raise ValueError(f"stop_checker: row {b} / end {end} outside [0, {B}) x [0, {done}]")
                     if b not in ended:
                         ended[b] = end
-                        finished[b] = 1
-                        out_ids[b, end:] = pad_id
-            if (use_eos or ended) and done < T and bool(finished.all().item()):
+                        buf.finished[b] = 1
+                        buf.out_ids[b, end:] = pad_id
+            if (use_eos or ended) and done < T and bool(buf.finished.all().item()):
                 break
-        mark(3)
-        layers_run = stats[0] * tc.num_hidden_layers
-        tm["decode_forwards"] = int(stats[0])
-        tm["launches_per_layer"] = (stats[1] / layers_run) if layers_run else None
-        tm["fused_attention_layers"], tm["standalone_attention_layers"] = int(stats[2]), int(stats[3])
-        check_waits()
-        if getattr(self, "_debug_keep", False):     # probe hook: the decode's state after the last step
-            self._debug_last = {"kc": kc, "vc": vc, "logits": logits, "x": xdec, "S": S, "cos": cosd, "sin": sind, "k_lo": k_lo,
-                                "nsplit": nsplit, "Tmax": Tmax, "out_ids": out_ids}
-        gen = out_ids[:, :done].to(torch.int64)
-        if use_eos and done > 0 and not ended:
-            # HF stops at the step where every row has finished: trim trailing all-pad columns generated past it
-            fin_col = self._first_all_finished(gen, eos_token_ids, pad_id)
-            gen = gen[:, :fin_col]
-            done = fin_col
-        elif ended and done > 0:
-            # the same, a row the stop checker ended finishing at the column the checker named (or at its EOS if that came first)
-            g = gen.cpu().numpy()
-            fin_at = np.full(B, done, dtype=np.int64)
-            for b in range(B):
-                hit = np.flatnonzero(np.isin(g[b], list(eos_token_ids))) if use_eos else np.empty(0, dtype=np.int64)
-                if hit.size:
-                    fin_at[b] = hit[0] + 1
-                if b in ended:
-                    fin_at[b] = min(fin_at[b], ended[b])
-            done = int(max(1, min(done, fin_at.max())))
-            gen = gen[:, :done]
-        prompt = torch.from_numpy(ids_rep).to(self.dev)
-        seqs = torch.cat([prompt, gen], dim=1)
-        if ev is not None:
-            torch.cuda.synchronize()
-            tm.update({"vit_ms": ev[0].elapsed_time(ev[1]), "prefill_ms": ev[1].elapsed_time(ev[2]),
-                       "decode_ms": ev[2].elapsed_time(ev[3])})
-        if lp is not None:
-            lp = Logprobs(lp.token[:, :done], lp.rank[:, :done], lp.top_ids[:, :done], lp.top[:, :done])
-        return GenerateOutput(sequences=seqs, margins=None if margins is None else margins[:, :done], n_steps=done,
-                              timings=tm, logprobs=lp, prompt_logprobs=plp)
+        return done, ended
 
     @staticmethod
     def _sampling_vectors(V: int, T: int, eos_token_ids, do_sample: bool, min_p, presence_penalty, frequency_penalty,
@@ -753,10 +829,7 @@ class O3VEngine:
         `rows_per_chunk` rows at a time (as completion_logps does); no [S, vocab] tensor is ever held."""
         B0, S, H = xs.shape
         V = self.cfg.text.vocab_size
-        out = Logprobs(token=torch.zeros((B0, S - 1), dtype=torch.float32, device=self.dev),
-                       rank=torch.zeros((B0, S - 1), dtype=torch.int32, device=self.dev),
-                       top_ids=torch.zeros((B0, S - 1, n), dtype=torch.int32, device=self.dev),
-                       top=torch.zeros((B0, S - 1, n), dtype=torch.float32, device=self.dev))
+        out = Logprobs.zeros(B0, S - 1, n, self.dev)
         if S < 2:
             return out
         tgt = torch.from_numpy(np.ascontiguousarray(ids[:, 1:].astype(np.int32))).to(self.dev)
@@ -816,29 +889,14 @@ class O3VEngine:
             if self.q3:
                 self._vit_plan_cache.clear()   # the resampled position table lives in the plan
 
-    @staticmethod
-    def _first_all_finished(gen: torch.Tensor, eos_ids, pad_id) -> int:
-        """Number of columns HF would have produced: up to and including the step at which the last row hit EOS."""
-        g = gen.cpu().numpy()
-        B, T = g.shape
-        fin_at = np.full(B, T, dtype=np.int64)
-        for b in range(B):
-            hit = np.flatnonzero(np.isin(g[b], list(eos_ids)))
-            if hit.size:
-                fin_at[b] = hit[0] + 1
-        return int(min(T, fin_at.max()))
-
     # ------------------------------------------------------------------------------------------ logits / logps
     @torch.no_grad()
     def forward_logits(self, input_ids, attention_mask=None, pixel_values=None, image_grid_thw=None, frames=None,
                        vis_embeds=None, pixel_values_videos=None, video_grid_thw=None, video_frames=None,
                        second_per_grid_ts=None) -> torch.Tensor:
         """model(input_ids, ...).logits bf16 [B,L,V] (R:grpo_trainer.py:375)."""
-        ids = np.asarray(input_ids.cpu() if torch.is_tensor(input_ids) else input_ids, dtype=np.int64)
+        ids, mask, pad = prompt_arrays(input_ids, attention_mask, check_left_padding=False)
         B, S = ids.shape
-        mask = np.ones_like(ids) if attention_mask is None else np.asarray(
-            attention_mask.cpu() if torch.is_tensor(attention_mask) else attention_mask, dtype=np.int64)
-        pad = (mask == 0).sum(axis=1)
         vis, grid, vgrid, n_img_rows = self._visual(pixel_values, image_grid_thw, frames, vis_embeds, pixel_values_videos, video_grid_thw,
                                                     video_frames)
         pos, _ = self._positions(ids, mask, grid, vgrid, second_per_grid_ts)
@@ -859,18 +917,13 @@ class O3VEngine:
         out, the G x T completion tokens run as one pass behind that prefix, and the lm_head + log-softmax touch only the
         G x T positions that are kept, `rows_per_chunk` rows of logits at a time (the reference materialises
         [G, S+T, vocab]: 12.8 GB at G=8, S+T=5.2k)."""
-        cfg, tc = self.cfg, self.cfg.text
-        ids = np.asarray(prompt_ids.cpu() if torch.is_tensor(prompt_ids) else prompt_ids, dtype=np.int64).reshape(1, -1)
+        tc = self.cfg.text
         comp = torch.as_tensor(completion_ids).to(torch.int64)
         if comp.dim() != 2:
             raise ValueError("completion_ids must be [G, T]")
         G, T = comp.shape
+        ids, mask, pad = prompt_arrays(prompt_ids, attention_mask)      # ONE prompt: [S] or [1, S]
         S = ids.shape[1]
-        mask = np.ones_like(ids) if attention_mask is None else np.asarray(
-            attention_mask.cpu() if torch.is_tensor(attention_mask) else attention_mask, dtype=np.int64).reshape(1, -1)
-        pad = (mask == 0).sum(axis=1)
-        if not (mask[0, pad[0]:] == 1).all():
-            raise ValueError("only left padding is supported (padding_side='left', R:grpo_trainer.py:546)")
         H = tc.hidden_size
         out = torch.empty((G, T), dtype=torch.float32, device=self.dev)
         if T == 0 or G == 0:
@@ -878,16 +931,15 @@ class O3VEngine:
         as_np = lambda g: None if g is None else np.asarray(g.cpu() if torch.is_tensor(g) else g, dtype=np.int64).reshape(-1, 3)
         grid, vgrid = as_np(image_grid_thw), as_np(video_grid_thw)
         if frames is not None:
-            ps = cfg.vision.patch_size
-            grid = np.asarray([[1, frames.shape[2] // ps, frames.shape[3] // ps]] * frames.shape[0], dtype=np.int64)
+            grid = self.frames_grid(frames)
         if video_frames is not None:
             vgrid = None      # derived from the frames by the tower's front end: no hand-over for this input form
         memo, self.timings_last_logps = self._last_prompt, {"prompt_kv_reused": False}
         pos = deltas = None
         if memo is not None and (video_frames is None):
             pos, deltas = self._positions(ids, mask, grid, vgrid, second_per_grid_ts)
-            key = self._prompt_key(ids, mask, pos, (("pv", pixel_values), ("grid", grid), ("frames", frames), ("vis", vis_embeds),
-                                                    ("pvv", pixel_values_videos), ("vgrid", vgrid), ("vframes", video_frames)))
+            key = self._prompt_key(ids, mask, pos, visual_identity(pixel_values, grid, frames, vis_embeds, pixel_values_videos, vgrid,
+                                                                   video_frames))
             if key != memo["key"]:
                 memo = None
         else:

@@ -537,3 +537,334 @@ def test_prompt_identity_key_for_the_generate_to_logps_hand_over():
     assert k1 == key(ids, mask, pos, (("frames", fr2),))
     fr2[2][1, 5, 5] ^= 4
     assert k1 != key(ids, mask, pos, (("frames", fr2),))
+
+
+# plan_decode: (Hq, Hkv, D, B0, G, S, T), switches -> (B, own_splits, shared_prompt, Tmax, nsplit, group, want_sync), produced by the
+# expressions of O3VEngine._generate as they stood before plan_decode existed (run on their own over these inputs)
+PLAN_TABLE = [
+    ((28, 4, 128, 1, 1, 4500, 256), {}, (1, 2, False, 4756, 38, 0, True)),
+    ((28, 4, 128, 1, 2, 4500, 256), {}, (2, 2, True, 256, -38, 2, False)),
+    ((28, 4, 128, 1, 3, 4500, 256), {}, (3, 2, True, 256, -38, 3, False)),
+    ((28, 4, 128, 1, 4, 4500, 256), {}, (4, 2, True, 256, -38, 4, False)),
+    ((28, 4, 128, 1, 8, 4500, 256), {}, (8, 2, True, 256, -20, 8, False)),
+    ((28, 4, 128, 1, 12, 4500, 256), {}, (12, 2, True, 256, -13, 12, False)),
+    ((28, 4, 128, 1, 16, 4500, 256), {}, (16, 2, True, 256, 20, 4, False)),
+    ((28, 4, 128, 1, 32, 4500, 256), {}, (32, 2, True, 256, 10, 4, False)),
+    ((28, 4, 128, 2, 4, 4500, 256), {}, (8, 2, True, 256, -20, 4, False)),
+    ((28, 4, 128, 4, 8, 4500, 256), {}, (32, 2, True, 256, 10, 4, False)),
+    ((28, 4, 128, 8, 1, 4500, 256), {}, (8, 2, False, 4756, 20, 0, False)),
+    ((28, 4, 128, 32, 1, 4500, 256), {}, (32, 2, False, 4756, 5, 0, False)),
+    ((16, 2, 128, 1, 1, 4500, 256), {}, (1, 2, False, 4756, 38, 0, True)),
+    ((16, 2, 128, 1, 2, 4500, 256), {}, (2, 2, True, 256, -38, 2, False)),
+    ((16, 2, 128, 1, 3, 4500, 256), {}, (3, 2, True, 256, -38, 3, False)),
+    ((16, 2, 128, 1, 4, 4500, 256), {}, (4, 2, True, 256, -38, 4, False)),
+    ((16, 2, 128, 1, 8, 4500, 256), {}, (8, 2, True, 256, -38, 8, False)),
+    ((16, 2, 128, 1, 12, 4500, 256), {}, (12, 2, True, 256, -26, 12, False)),
+    ((16, 2, 128, 1, 16, 4500, 256), {}, (16, 2, True, 256, 36, 4, False)),
+    ((16, 2, 128, 1, 32, 4500, 256), {}, (32, 2, True, 256, 20, 4, False)),
+    ((16, 2, 128, 2, 4, 4500, 256), {}, (8, 2, True, 256, -38, 4, False)),
+    ((16, 2, 128, 4, 8, 4500, 256), {}, (32, 2, True, 256, 20, 4, False)),
+    ((16, 2, 128, 8, 1, 4500, 256), {}, (8, 2, False, 4756, 38, 0, False)),
+    ((16, 2, 128, 32, 1, 4500, 256), {}, (32, 2, False, 4756, 10, 0, False)),
+    ((32, 8, 128, 1, 1, 4500, 256), {}, (1, 2, False, 4756, 38, 0, True)),
+    ((32, 8, 128, 1, 2, 4500, 256), {}, (2, 2, True, 256, -38, 2, False)),
+    ((32, 8, 128, 1, 3, 4500, 256), {}, (3, 2, True, 256, -26, 3, False)),
+    ((32, 8, 128, 1, 4, 4500, 256), {}, (4, 2, True, 256, -20, 4, False)),
+    ((32, 8, 128, 1, 8, 4500, 256), {}, (8, 2, True, 256, -10, 8, False)),
+    ((32, 8, 128, 1, 12, 4500, 256), {}, (12, 2, True, 256, -6, 12, False)),
+    ((32, 8, 128, 1, 16, 4500, 256), {}, (16, 2, True, 256, 10, 4, False)),
+    ((32, 8, 128, 1, 32, 4500, 256), {}, (32, 2, True, 256, 5, 4, False)),
+    ((32, 8, 128, 2, 4, 4500, 256), {}, (8, 2, True, 256, -10, 4, False)),
+    ((32, 8, 128, 4, 8, 4500, 256), {}, (32, 2, True, 256, 5, 4, False)),
+    ((32, 8, 128, 8, 1, 4500, 256), {}, (8, 2, False, 4756, 10, 0, False)),
+    ((32, 8, 128, 32, 1, 4500, 256), {}, (32, 2, False, 4756, 2, 0, False)),
+    ((4, 2, 64, 1, 1, 4500, 256), {}, (1, 2, False, 4756, 38, 0, True)),
+    ((4, 2, 64, 1, 2, 4500, 256), {}, (2, 2, False, 4756, 38, 0, False)),
+    ((4, 2, 64, 1, 3, 4500, 256), {}, (3, 2, False, 4756, 38, 0, False)),
+    ((4, 2, 64, 1, 4, 4500, 256), {}, (4, 2, False, 4756, 38, 0, False)),
+    ((4, 2, 64, 1, 8, 4500, 256), {}, (8, 2, False, 4756, 38, 0, False)),
+    ((4, 2, 64, 1, 12, 4500, 256), {}, (12, 2, False, 4756, 26, 0, False)),
+    ((4, 2, 64, 1, 16, 4500, 256), {}, (16, 2, False, 4756, 20, 0, False)),
+    ((4, 2, 64, 1, 32, 4500, 256), {}, (32, 2, False, 4756, 10, 0, False)),
+    ((4, 2, 64, 2, 4, 4500, 256), {}, (8, 2, False, 4756, 38, 0, False)),
+    ((4, 2, 64, 4, 8, 4500, 256), {}, (32, 2, False, 4756, 10, 0, False)),
+    ((4, 2, 64, 8, 1, 4500, 256), {}, (8, 2, False, 4756, 38, 0, False)),
+    ((4, 2, 64, 32, 1, 4500, 256), {}, (32, 2, False, 4756, 10, 0, False)),
+    ((28, 4, 128, 1, 1, 127, 1), {}, (1, 1, False, 128, 1, 0, True)),
+    ((28, 4, 128, 1, 8, 127, 1), {}, (8, 1, True, 1, -1, 8, False)),
+    ((28, 4, 128, 1, 16, 127, 1), {}, (16, 1, True, 1, 1, 4, False)),
+    ((28, 4, 128, 1, 1, 127, 128), {}, (1, 1, False, 255, 2, 0, True)),
+    ((28, 4, 128, 1, 8, 127, 128), {}, (8, 1, True, 128, -2, 8, False)),
+    ((28, 4, 128, 1, 16, 127, 128), {}, (16, 1, True, 128, 1, 4, False)),
+    ((28, 4, 128, 1, 1, 127, 129), {}, (1, 2, False, 256, 2, 0, True)),
+    ((28, 4, 128, 1, 8, 127, 129), {}, (8, 2, True, 129, -2, 8, False)),
+    ((28, 4, 128, 1, 16, 127, 129), {}, (16, 2, True, 129, 1, 4, False)),
+    ((28, 4, 128, 1, 1, 127, 256), {}, (1, 2, False, 383, 3, 0, True)),
+    ((28, 4, 128, 1, 8, 127, 256), {}, (8, 2, True, 256, -3, 8, False)),
+    ((28, 4, 128, 1, 16, 127, 256), {}, (16, 2, True, 256, 1, 4, False)),
+    ((28, 4, 128, 1, 1, 127, 4096), {}, (1, 32, False, 4223, 33, 0, True)),
+    ((28, 4, 128, 1, 8, 127, 4096), {}, (8, 32, True, 4096, -20, 8, False)),
+    ((28, 4, 128, 1, 16, 127, 4096), {}, (16, 32, True, 4096, 1, 4, False)),
+    ((28, 4, 128, 1, 1, 127, 4097), {}, (1, 33, False, 4224, 33, 0, True)),
+    ((28, 4, 128, 1, 8, 127, 4097), {}, (8, 33, False, 4224, 20, 0, False)),
+    ((28, 4, 128, 1, 16, 127, 4097), {}, (16, 33, False, 4224, 10, 0, False)),
+    ((28, 4, 128, 1, 1, 128, 1), {}, (1, 1, False, 129, 2, 0, True)),
+    ((28, 4, 128, 1, 8, 128, 1), {}, (8, 1, True, 1, -2, 8, False)),
+    ((28, 4, 128, 1, 16, 128, 1), {}, (16, 1, True, 1, 1, 4, False)),
+    ((28, 4, 128, 1, 1, 128, 128), {}, (1, 1, False, 256, 2, 0, True)),
+    ((28, 4, 128, 1, 8, 128, 128), {}, (8, 1, True, 128, -2, 8, False)),
+    ((28, 4, 128, 1, 16, 128, 128), {}, (16, 1, True, 128, 1, 4, False)),
+    ((28, 4, 128, 1, 1, 128, 129), {}, (1, 2, False, 257, 3, 0, True)),
+    ((28, 4, 128, 1, 8, 128, 129), {}, (8, 2, True, 129, -3, 8, False)),
+    ((28, 4, 128, 1, 16, 128, 129), {}, (16, 2, True, 129, 1, 4, False)),
+    ((28, 4, 128, 1, 1, 128, 256), {}, (1, 2, False, 384, 3, 0, True)),
+    ((28, 4, 128, 1, 8, 128, 256), {}, (8, 2, True, 256, -3, 8, False)),
+    ((28, 4, 128, 1, 16, 128, 256), {}, (16, 2, True, 256, 1, 4, False)),
+    ((28, 4, 128, 1, 1, 128, 4096), {}, (1, 32, False, 4224, 33, 0, True)),
+    ((28, 4, 128, 1, 8, 128, 4096), {}, (8, 32, True, 4096, -20, 8, False)),
+    ((28, 4, 128, 1, 16, 128, 4096), {}, (16, 32, True, 4096, 1, 4, False)),
+    ((28, 4, 128, 1, 1, 128, 4097), {}, (1, 33, False, 4225, 34, 0, True)),
+    ((28, 4, 128, 1, 8, 128, 4097), {}, (8, 33, False, 4225, 20, 0, False)),
+    ((28, 4, 128, 1, 16, 128, 4097), {}, (16, 33, False, 4225, 10, 0, False)),
+    ((28, 4, 128, 1, 1, 129, 1), {}, (1, 1, False, 130, 2, 0, True)),
+    ((28, 4, 128, 1, 8, 129, 1), {}, (8, 1, True, 1, -2, 8, False)),
+    ((28, 4, 128, 1, 16, 129, 1), {}, (16, 1, True, 1, 2, 4, False)),
+    ((28, 4, 128, 1, 1, 129, 128), {}, (1, 1, False, 257, 3, 0, True)),
+    ((28, 4, 128, 1, 8, 129, 128), {}, (8, 1, True, 128, -3, 8, False)),
+    ((28, 4, 128, 1, 16, 129, 128), {}, (16, 1, True, 128, 2, 4, False)),
+    ((28, 4, 128, 1, 1, 129, 129), {}, (1, 2, False, 258, 3, 0, True)),
+    ((28, 4, 128, 1, 8, 129, 129), {}, (8, 2, True, 129, -3, 8, False)),
+    ((28, 4, 128, 1, 16, 129, 129), {}, (16, 2, True, 129, 2, 4, False)),
+    ((28, 4, 128, 1, 1, 129, 256), {}, (1, 2, False, 385, 4, 0, True)),
+    ((28, 4, 128, 1, 8, 129, 256), {}, (8, 2, True, 256, -4, 8, False)),
+    ((28, 4, 128, 1, 16, 129, 256), {}, (16, 2, True, 256, 2, 4, False)),
+    ((28, 4, 128, 1, 1, 129, 4096), {}, (1, 32, False, 4225, 34, 0, True)),
+    ((28, 4, 128, 1, 8, 129, 4096), {}, (8, 32, True, 4096, -20, 8, False)),
+    ((28, 4, 128, 1, 16, 129, 4096), {}, (16, 32, True, 4096, 2, 4, False)),
+    ((28, 4, 128, 1, 1, 129, 4097), {}, (1, 33, False, 4226, 34, 0, True)),
+    ((28, 4, 128, 1, 8, 129, 4097), {}, (8, 33, False, 4226, 20, 0, False)),
+    ((28, 4, 128, 1, 16, 129, 4097), {}, (16, 33, False, 4226, 10, 0, False)),
+    ((28, 4, 128, 1, 1, 4500, 1), {}, (1, 1, False, 4501, 36, 0, True)),
+    ((28, 4, 128, 1, 8, 4500, 1), {}, (8, 1, True, 1, -20, 8, False)),
+    ((28, 4, 128, 1, 16, 4500, 1), {}, (16, 1, True, 1, 20, 4, False)),
+    ((28, 4, 128, 1, 1, 4500, 128), {}, (1, 1, False, 4628, 37, 0, True)),
+    ((28, 4, 128, 1, 8, 4500, 128), {}, (8, 1, True, 128, -20, 8, False)),
+    ((28, 4, 128, 1, 16, 4500, 128), {}, (16, 1, True, 128, 20, 4, False)),
+    ((28, 4, 128, 1, 1, 4500, 129), {}, (1, 2, False, 4629, 37, 0, True)),
+    ((28, 4, 128, 1, 8, 4500, 129), {}, (8, 2, True, 129, -20, 8, False)),
+    ((28, 4, 128, 1, 16, 4500, 129), {}, (16, 2, True, 129, 20, 4, False)),
+    ((28, 4, 128, 1, 1, 4500, 4096), {}, (1, 32, False, 8596, 64, 0, True)),
+    ((28, 4, 128, 1, 8, 4500, 4096), {}, (8, 32, True, 4096, -20, 8, False)),
+    ((28, 4, 128, 1, 16, 4500, 4096), {}, (16, 32, True, 4096, 20, 4, False)),
+    ((28, 4, 128, 1, 1, 4500, 4097), {}, (1, 33, False, 8597, 64, 0, True)),
+    ((28, 4, 128, 1, 8, 4500, 4097), {}, (8, 33, False, 8597, 20, 0, False)),
+    ((28, 4, 128, 1, 16, 4500, 4097), {}, (16, 33, False, 8597, 10, 0, False)),
+    ((28, 4, 128, 1, 1, 8191, 1), {}, (1, 1, False, 8192, 64, 0, True)),
+    ((28, 4, 128, 1, 8, 8191, 1), {}, (8, 1, True, 1, -20, 8, False)),
+    ((28, 4, 128, 1, 16, 8191, 1), {}, (16, 1, True, 1, 20, 4, False)),
+    ((28, 4, 128, 1, 1, 8191, 128), {}, (1, 1, False, 8319, 64, 0, True)),
+    ((28, 4, 128, 1, 8, 8191, 128), {}, (8, 1, True, 128, -20, 8, False)),
+    ((28, 4, 128, 1, 16, 8191, 128), {}, (16, 1, True, 128, 20, 4, False)),
+    ((28, 4, 128, 1, 1, 8191, 129), {}, (1, 2, False, 8320, 64, 0, True)),
+    ((28, 4, 128, 1, 8, 8191, 129), {}, (8, 2, True, 129, -20, 8, False)),
+    ((28, 4, 128, 1, 16, 8191, 129), {}, (16, 2, True, 129, 20, 4, False)),
+    ((28, 4, 128, 1, 1, 8191, 256), {}, (1, 2, False, 8447, 64, 0, True)),
+    ((28, 4, 128, 1, 8, 8191, 256), {}, (8, 2, True, 256, -20, 8, False)),
+    ((28, 4, 128, 1, 16, 8191, 256), {}, (16, 2, True, 256, 20, 4, False)),
+    ((28, 4, 128, 1, 1, 8191, 4096), {}, (1, 32, False, 12287, 64, 0, True)),
+    ((28, 4, 128, 1, 8, 8191, 4096), {}, (8, 32, True, 4096, -20, 8, False)),
+    ((28, 4, 128, 1, 16, 8191, 4096), {}, (16, 32, True, 4096, 20, 4, False)),
+    ((28, 4, 128, 1, 1, 8191, 4097), {}, (1, 33, False, 12288, 64, 0, True)),
+    ((28, 4, 128, 1, 8, 8191, 4097), {}, (8, 33, False, 12288, 20, 0, False)),
+    ((28, 4, 128, 1, 16, 8191, 4097), {}, (16, 33, False, 12288, 10, 0, False)),
+    ((28, 4, 128, 1, 1, 8192, 1), {}, (1, 1, False, 8193, 64, 0, True)),
+    ((28, 4, 128, 1, 8, 8192, 1), {}, (8, 1, True, 1, 63, 4, False)),
+    ((28, 4, 128, 1, 16, 8192, 1), {}, (16, 1, True, 1, 63, 4, False)),
+    ((28, 4, 128, 1, 1, 8192, 128), {}, (1, 1, False, 8320, 64, 0, True)),
+    ((28, 4, 128, 1, 8, 8192, 128), {}, (8, 1, True, 128, 63, 4, False)),
+    ((28, 4, 128, 1, 16, 8192, 128), {}, (16, 1, True, 128, 63, 4, False)),
+    ((28, 4, 128, 1, 1, 8192, 129), {}, (1, 2, False, 8321, 64, 0, True)),
+    ((28, 4, 128, 1, 8, 8192, 129), {}, (8, 2, True, 129, 62, 4, False)),
+    ((28, 4, 128, 1, 16, 8192, 129), {}, (16, 2, True, 129, 62, 4, False)),
+    ((28, 4, 128, 1, 1, 8192, 256), {}, (1, 2, False, 8448, 64, 0, True)),
+    ((28, 4, 128, 1, 8, 8192, 256), {}, (8, 2, True, 256, 62, 4, False)),
+    ((28, 4, 128, 1, 16, 8192, 256), {}, (16, 2, True, 256, 62, 4, False)),
+    ((28, 4, 128, 1, 1, 8192, 4096), {}, (1, 32, False, 12288, 64, 0, True)),
+    ((28, 4, 128, 1, 8, 8192, 4096), {}, (8, 32, True, 4096, 32, 4, False)),
+    ((28, 4, 128, 1, 16, 8192, 4096), {}, (16, 32, True, 4096, 32, 4, False)),
+    ((28, 4, 128, 1, 1, 8192, 4097), {}, (1, 33, False, 12289, 64, 0, True)),
+    ((28, 4, 128, 1, 8, 8192, 4097), {}, (8, 33, False, 12289, 20, 0, False)),
+    ((28, 4, 128, 1, 16, 8192, 4097), {}, (16, 33, False, 12289, 10, 0, False)),
+    ((28, 4, 128, 1, 1, 10000, 1), {}, (1, 1, False, 10001, 64, 0, True)),
+    ((28, 4, 128, 1, 8, 10000, 1), {}, (8, 1, True, 1, 63, 4, False)),
+    ((28, 4, 128, 1, 16, 10000, 1), {}, (16, 1, True, 1, 63, 4, False)),
+    ((28, 4, 128, 1, 1, 10000, 128), {}, (1, 1, False, 10128, 64, 0, True)),
+    ((28, 4, 128, 1, 8, 10000, 128), {}, (8, 1, True, 128, 63, 4, False)),
+    ((28, 4, 128, 1, 16, 10000, 128), {}, (16, 1, True, 128, 63, 4, False)),
+    ((28, 4, 128, 1, 1, 10000, 129), {}, (1, 2, False, 10129, 64, 0, True)),
+    ((28, 4, 128, 1, 8, 10000, 129), {}, (8, 2, True, 129, 62, 4, False)),
+    ((28, 4, 128, 1, 16, 10000, 129), {}, (16, 2, True, 129, 62, 4, False)),
+    ((28, 4, 128, 1, 1, 10000, 256), {}, (1, 2, False, 10256, 64, 0, True)),
+    ((28, 4, 128, 1, 8, 10000, 256), {}, (8, 2, True, 256, 62, 4, False)),
+    ((28, 4, 128, 1, 16, 10000, 256), {}, (16, 2, True, 256, 62, 4, False)),
+    ((28, 4, 128, 1, 1, 10000, 4096), {}, (1, 32, False, 14096, 64, 0, True)),
+    ((28, 4, 128, 1, 8, 10000, 4096), {}, (8, 32, True, 4096, 32, 4, False)),
+    ((28, 4, 128, 1, 16, 10000, 4096), {}, (16, 32, True, 4096, 32, 4, False)),
+    ((28, 4, 128, 1, 1, 10000, 4097), {}, (1, 33, False, 14097, 64, 0, True)),
+    ((28, 4, 128, 1, 8, 10000, 4097), {}, (8, 33, False, 14097, 20, 0, False)),
+    ((28, 4, 128, 1, 16, 10000, 4097), {}, (16, 33, False, 14097, 10, 0, False)),
+    ((28, 4, 128, 1, 4, 4500, 256), dict(group_attention_mode='kernel'), (4, 2, True, 256, 36, 4, False)),
+    ((28, 4, 128, 1, 4, 4500, 256), dict(group_attention_mode='shared_read'), (4, 2, True, 256, -38, 4, False)),
+    ((28, 4, 128, 1, 4, 4500, 256), dict(group_attention=False), (4, 2, False, 4756, 38, 0, False)),
+    ((28, 4, 128, 1, 4, 4500, 256), dict(nsplit_override=7), (4, 2, True, 256, -7, 4, False)),
+    ((28, 4, 128, 1, 4, 4500, 256), dict(fused=False), (4, 2, True, 256, -38, 4, False)),
+    ((28, 4, 128, 1, 4, 4500, 256), dict(tail_norm=True), (4, 2, True, 256, -38, 4, False)),
+    ((28, 4, 128, 1, 4, 4500, 256), dict(fused=False, tail_norm=True), (4, 2, True, 256, -38, 4, False)),
+    ((28, 4, 128, 1, 4, 10000, 256), dict(group_attention_mode='kernel'), (4, 2, True, 256, 62, 4, False)),
+    ((28, 4, 128, 1, 4, 10000, 256), dict(group_attention_mode='shared_read'), (4, 2, True, 256, -40, 4, False)),
+    ((28, 4, 128, 1, 4, 10000, 256), dict(group_attention=False), (4, 2, False, 10256, 40, 0, False)),
+    ((28, 4, 128, 1, 4, 10000, 256), dict(nsplit_override=7), (4, 2, True, 256, 62, 4, False)),
+    ((28, 4, 128, 1, 4, 10000, 256), dict(fused=False), (4, 2, True, 256, 62, 4, False)),
+    ((28, 4, 128, 1, 4, 10000, 256), dict(tail_norm=True), (4, 2, True, 256, 62, 4, False)),
+    ((28, 4, 128, 1, 4, 10000, 256), dict(fused=False, tail_norm=True), (4, 2, True, 256, 62, 4, False)),
+    ((28, 4, 128, 1, 8, 4500, 256), dict(group_attention_mode='kernel'), (8, 2, True, 256, 36, 4, False)),
+    ((28, 4, 128, 1, 8, 4500, 256), dict(group_attention_mode='shared_read'), (8, 2, True, 256, -20, 8, False)),
+    ((28, 4, 128, 1, 8, 4500, 256), dict(group_attention=False), (8, 2, False, 4756, 20, 0, False)),
+    ((28, 4, 128, 1, 8, 4500, 256), dict(nsplit_override=7), (8, 2, True, 256, -7, 8, False)),
+    ((28, 4, 128, 1, 8, 4500, 256), dict(fused=False), (8, 2, True, 256, -20, 8, False)),
+    ((28, 4, 128, 1, 8, 4500, 256), dict(tail_norm=True), (8, 2, True, 256, -20, 8, True)),
+    ((28, 4, 128, 1, 8, 4500, 256), dict(fused=False, tail_norm=True), (8, 2, True, 256, -20, 8, False)),
+    ((28, 4, 128, 1, 8, 10000, 256), dict(group_attention_mode='kernel'), (8, 2, True, 256, 62, 4, False)),
+    ((28, 4, 128, 1, 8, 10000, 256), dict(group_attention_mode='shared_read'), (8, 2, True, 256, -20, 8, False)),
+    ((28, 4, 128, 1, 8, 10000, 256), dict(group_attention=False), (8, 2, False, 10256, 20, 0, False)),
+    ((28, 4, 128, 1, 8, 10000, 256), dict(nsplit_override=7), (8, 2, True, 256, 62, 4, False)),
+    ((28, 4, 128, 1, 8, 10000, 256), dict(fused=False), (8, 2, True, 256, 62, 4, False)),
+    ((28, 4, 128, 1, 8, 10000, 256), dict(tail_norm=True), (8, 2, True, 256, 62, 4, True)),
+    ((28, 4, 128, 1, 8, 10000, 256), dict(fused=False, tail_norm=True), (8, 2, True, 256, 62, 4, False)),
+    ((28, 4, 128, 1, 16, 4500, 256), dict(group_attention_mode='kernel'), (16, 2, True, 256, 20, 4, False)),
+    ((28, 4, 128, 1, 16, 4500, 256), dict(group_attention_mode='shared_read'), (16, 2, True, 256, -10, 16, False)),
+    ((28, 4, 128, 1, 16, 4500, 256), dict(group_attention=False), (16, 2, False, 4756, 10, 0, False)),
+    ((28, 4, 128, 1, 16, 4500, 256), dict(nsplit_override=7), (16, 2, True, 256, 20, 4, False)),
+    ((28, 4, 128, 1, 16, 4500, 256), dict(fused=False), (16, 2, True, 256, 20, 4, False)),
+    ((28, 4, 128, 1, 16, 4500, 256), dict(tail_norm=True), (16, 2, True, 256, 20, 4, True)),
+    ((28, 4, 128, 1, 16, 4500, 256), dict(fused=False, tail_norm=True), (16, 2, True, 256, 20, 4, False)),
+    ((28, 4, 128, 1, 16, 10000, 256), dict(group_attention_mode='kernel'), (16, 2, True, 256, 62, 4, False)),
+    ((28, 4, 128, 1, 16, 10000, 256), dict(group_attention_mode='shared_read'), (16, 2, True, 256, -10, 16, False)),
+    ((28, 4, 128, 1, 16, 10000, 256), dict(group_attention=False), (16, 2, False, 10256, 10, 0, False)),
+    ((28, 4, 128, 1, 16, 10000, 256), dict(nsplit_override=7), (16, 2, True, 256, 62, 4, False)),
+    ((28, 4, 128, 1, 16, 10000, 256), dict(fused=False), (16, 2, True, 256, 62, 4, False)),
+    ((28, 4, 128, 1, 16, 10000, 256), dict(tail_norm=True), (16, 2, True, 256, 62, 4, True)),
+    ((28, 4, 128, 1, 16, 10000, 256), dict(fused=False, tail_norm=True), (16, 2, True, 256, 62, 4, False)),
+    ((28, 4, 128, 8, 1, 4500, 256), dict(group_attention_mode='kernel'), (8, 2, False, 4756, 20, 0, False)),
+    ((28, 4, 128, 8, 1, 4500, 256), dict(group_attention_mode='shared_read'), (8, 2, False, 4756, 20, 0, False)),
+    ((28, 4, 128, 8, 1, 4500, 256), dict(group_attention=False), (8, 2, False, 4756, 20, 0, False)),
+    ((28, 4, 128, 8, 1, 4500, 256), dict(nsplit_override=7), (8, 2, False, 4756, 7, 0, False)),
+    ((28, 4, 128, 8, 1, 4500, 256), dict(fused=False), (8, 2, False, 4756, 20, 0, False)),
+    ((28, 4, 128, 8, 1, 4500, 256), dict(tail_norm=True), (8, 2, False, 4756, 20, 0, True)),
+    ((28, 4, 128, 8, 1, 4500, 256), dict(fused=False, tail_norm=True), (8, 2, False, 4756, 20, 0, False)),
+    ((28, 4, 128, 8, 1, 10000, 256), dict(group_attention_mode='kernel'), (8, 2, False, 10256, 20, 0, False)),
+    ((28, 4, 128, 8, 1, 10000, 256), dict(group_attention_mode='shared_read'), (8, 2, False, 10256, 20, 0, False)),
+    ((28, 4, 128, 8, 1, 10000, 256), dict(group_attention=False), (8, 2, False, 10256, 20, 0, False)),
+    ((28, 4, 128, 8, 1, 10000, 256), dict(nsplit_override=7), (8, 2, False, 10256, 7, 0, False)),
+    ((28, 4, 128, 8, 1, 10000, 256), dict(fused=False), (8, 2, False, 10256, 20, 0, False)),
+    ((28, 4, 128, 8, 1, 10000, 256), dict(tail_norm=True), (8, 2, False, 10256, 20, 0, True)),
+    ((28, 4, 128, 8, 1, 10000, 256), dict(fused=False, tail_norm=True), (8, 2, False, 10256, 20, 0, False)),
+    ((16, 2, 128, 1, 1, 4500, 256), dict(fused=False), (1, 2, False, 4756, 38, 0, False)),
+    ((16, 2, 128, 1, 16, 10000, 256), dict(group_attention_mode='kernel', nsplit_override=7), (16, 2, True, 256, 62, 4, False)),
+]
+
+
+def test_plan_decode_matches_the_recorded_table():
+    """engine.plan_decode (the decode attention plan of a generate call: rows, shared prompt K/V, cache slots, context splits and
+    their sign, group size, hand-off buffer) against rows recorded from the in-line arithmetic it replaces: the 7B / 3B /
+    Qwen3-VL-8B / head_dim-64 geometries x every (B0, G) shape, the S and T edges (127..129 keys, the 8192 kernel threshold,
+    T = 4097 -> 33 own splits -> no shared prompt), the three group modes, group attention off, an O3V_NSPLIT override (applied
+    before the group branch: the kernel mode recomputes it, shared-read negates it), and fused / tail_norm on and off."""
+    from open_o3_video_amd.engine import DecodePlan, plan_decode
+    assert DecodePlan._fields == ("B", "own_splits", "shared_prompt", "Tmax", "nsplit", "group", "want_sync")
+    for args, kw, want in PLAN_TABLE:
+        got = plan_decode(*args, **kw)
+        assert tuple(got) == want and isinstance(got, DecodePlan), (args, kw, tuple(got), want)
+    covered = {a[:3] for a, _, _ in PLAN_TABLE}
+    assert covered >= {(28, 4, 128), (16, 2, 128), (32, 8, 128), (4, 2, 64)}
+    assert {a[3:5] for a, _, _ in PLAN_TABLE} >= {(1, 1), (1, 2), (1, 3), (1, 4), (1, 8), (1, 12), (1, 16), (1, 32), (2, 4), (4, 8), (8, 1),
+                                                  (32, 1)}
+    assert {a[5] for a, _, _ in PLAN_TABLE} >= {127, 128, 129, 4500, 8191, 8192, 10000}
+    assert {a[6] for a, _, _ in PLAN_TABLE} >= {1, 128, 129, 256, 4096, 4097}
+    # rows named when plan_decode was specified: (B, shared_prompt, Tmax, nsplit, group, want_sync)
+    for args, want in {(28, 4, 128, 1, 1, 4500, 256): (1, False, 4756, 38, 0, True),
+                       (28, 4, 128, 1, 8, 4500, 256): (8, True, 256, -20, 8, False),
+                       (28, 4, 128, 1, 16, 4500, 256): (16, True, 256, 20, 4, False),
+                       (28, 4, 128, 1, 8, 10000, 256): (8, True, 256, 62, 4, False),
+                       (28, 4, 128, 2, 4, 300, 5000): (8, False, 5300, 20, 0, False),
+                       (16, 2, 128, 1, 8, 4500, 256): (8, True, 256, -38, 8, False),
+                       (32, 8, 128, 1, 12, 4500, 256): (12, True, 256, -6, 12, False),
+                       (4, 2, 64, 1, 4, 40, 8): (4, False, 48, 1, 0, False),
+                       (28, 4, 128, 1, 3, 200, 16): (3, True, 16, -2, 3, False)}.items():
+        p = plan_decode(*args)
+        assert (p.B, p.shared_prompt, p.Tmax, p.nsplit, p.group, p.want_sync) == want, (args, p)
+        assert p.own_splits == (args[6] + 127) // 128
+
+
+def test_trimmed_length_against_brute_force():
+    """engine.trimmed_length (columns kept of a decode's [B, done] ids) against its definition: a row ends at whichever comes first
+    of its first EOS column + 1, the column the stop checker named for it (ended[b]), or done; the result is the largest such end,
+    clamped to [1, done]."""
+    from open_o3_video_amd.engine import trimmed_length
+
+    def brute(gen, eos_ids, ended, done):
+        ends = []
+        for b in range(gen.shape[0]):
+            end = done
+            for j in range(done):
+                if int(gen[b, j]) in eos_ids:
+                    end = j + 1
+                    break
+            if b in ended:
+                end = min(end, ended[b])
+            ends.append(end)
+        return min(done, max(1, max(ends)))
+
+    rng = np.random.default_rng(11)
+    n = 0
+    for trial in range(600):
+        B, done = int(rng.integers(1, 5)), int(rng.integers(1, 13))
+        gen = rng.integers(0, 6, size=(B, done)).astype(np.int64)
+        eos = [(), (5,), (4, 5)][trial % 3]
+        ended = {int(b): int(rng.integers(0, done + 1)) for b in range(B) if rng.random() < 0.4} if trial % 2 else {}
+        assert trimmed_length(gen, eos, ended, done) == brute(gen, set(eos), ended, done), (gen, eos, ended, done)
+        n += 1
+    assert n == 600
+    g = np.asarray([[1, 2, 5, 0, 0, 0], [1, 1, 1, 1, 1, 1]], dtype=np.int64)
+    assert trimmed_length(g, (5,), {}, 6) == 6                       # a row that never ends
+    assert trimmed_length(g[:1], (5,), {}, 6) == 3                   # every row at its EOS
+    assert trimmed_length(g[:1], (), {0: 0}, 6) == 1                 # ended[b] = 0: one column stays
+    assert trimmed_length(g, (5,), {1: 0}, 6) == 3
+    assert trimmed_length(g[:1], (5,), {0: 4}, 6) == 3               # an EOS before ended[b]
+    assert trimmed_length(g[:1], (5,), {0: 2}, 6) == 2               # an EOS after ended[b]
+    assert trimmed_length(g, (), {0: 2, 1: 4}, 6) == 4
+    assert trimmed_length(g, (), {0: 2}, 6) == 6
+    assert isinstance(trimmed_length(g, (5,), {}, 6), int)
+
+
+def test_prompt_arrays():
+    """engine.prompt_arrays (what generate, forward_logits and completion_logps make of input_ids / attention_mask): tensor, list and
+    1-D input, a missing mask, left padding; right padding raises unless the check is off (forward_logits)."""
+    from open_o3_video_amd.engine import prompt_arrays
+    rows = [[7, 8, 9, 10], [1, 2, 3, 4]]
+    left = [[0, 0, 1, 1], [1, 1, 1, 1]]
+    for conv in (list, np.asarray, torch.tensor, lambda a: torch.tensor(a, dtype=torch.int32)):
+        ids, mask, pad = prompt_arrays(conv(rows), conv(left))
+        assert ids.dtype == mask.dtype == np.int64 and ids.shape == mask.shape == (2, 4)
+        assert ids.tolist() == rows and mask.tolist() == left and pad.tolist() == [2, 0]
+    ids, mask, pad = prompt_arrays(rows)
+    assert mask.tolist() == [[1] * 4] * 2 and mask.dtype == np.int64 and pad.tolist() == [0, 0]
+    for one in (rows[0], np.asarray(rows[0]), torch.tensor(rows[0])):
+        ids, mask, pad = prompt_arrays(one, left[0])
+        assert ids.shape == mask.shape == (1, 4) and ids.tolist() == [rows[0]] and mask.tolist() == [left[0]] and pad.tolist() == [2]
+        assert prompt_arrays(one)[1].tolist() == [[1] * 4]
+    for bad, n_masked in (([[1, 1, 0, 0], [1, 1, 1, 1]], [2, 0]), ([[1, 1, 1, 1], [0, 1, 0, 1]], [0, 2])):
+        with pytest.raises(ValueError, match=r"only left padding is supported \(padding_side='left', R:grpo_trainer.py:546\)"):
+            prompt_arrays(rows, bad)
+        ids, mask, pad = prompt_arrays(rows, bad, check_left_padding=False)
+        assert mask.tolist() == bad and pad.tolist() == n_masked
