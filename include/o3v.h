@@ -544,15 +544,49 @@ typedef struct {
      * attention half ran as the one-launch block, layers whose attention half ran on the stand-alone kernels */
     long long* host_stats;
     int flags;                   /* O3V_DECODE_* below, or'ed */
+    /* optional fp8 K/V cache (all four or none; independent rows only: group <= 1, no kprefix; head_dim 128; nsplit > 0).
+     * k8 / v8: u8 [layers][B][Hkv][Tmax][128] OCP e4m3fn codes, k8s / v8s: f32 [layers][B][Hkv][Tmax], one power-of-two scale per
+     * (token, kv head) row (o3v_kv8_quantize).  kcache / vcache are then bf16 STAGING rows [B][Hkv][1][128], one layer's worth reused
+     * by every layer: q/k/v writes the new token's K/V there (Tmax = 1, slot 0) and o3v_attn_decode_kv8 quantises it into slot
+     * S + step.  The attention half runs on the stand-alone kernels (no one-launch block at B = 1).  NULL: off. */
+    void *k8, *v8;
+    float *k8s, *v8s;
 } o3v_decode_state;
 /* o3v_decode_state.flags.  LAYER_BLOCK: batch-1 bf16 decode may use the persistent layer block (o3v_decode_layer_block) where its
  * shapes allow, then one launch for the attention half + gate/up and one for down_proj per layer; otherwise o3v_decode_attn_block +
  * two launches.  NO_TAIL_NORM (inverted: set = off): at 8..32 bf16 rows with `sync` given, o_proj / down_proj do NOT normalise their
  * result for the linear that follows (o3v_linear_decode_norm_next); the norms are launches of their own.  NO_QKV_FUSED_NORM (inverted
- * as well): at 8 rows q/k/v does NOT take its RMSNorm fused; the norm is a launch of its own as at 9..32 rows. */
+ * as well): at 8 rows q/k/v does NOT take its RMSNorm fused; the norm is a launch of its own as at 9..32 rows.
+ * KV8_EMULATE (tests; k8 == NULL, an ordinary bf16 cache): after q/k/v of every layer the new token's K/V rows are replaced by
+ * dequant(quant(row)) (o3v_kv8_roundtrip, one more launch per layer) and the attention half runs on the stand-alone bf16 kernels:
+ * the arithmetic of the fp8 K/V cache, bit for bit, on the bf16 kernels. */
 #define O3V_DECODE_LAYER_BLOCK 1
 #define O3V_DECODE_NO_TAIL_NORM 2
 #define O3V_DECODE_NO_QKV_FUSED_NORM 4
+#define O3V_DECODE_KV8_EMULATE 8
+
+/* ---- opt-in fp8 K/V cache of the independent-row decode (vLLM kv_cache_dtype="fp8"; head_dim 128) --------------------------------
+ * Storage: codes u8 [heads][Tmax][128] (OCP e4m3fn) + scales f32 [heads][Tmax], heads = (layers x) B x Hkv; 132 bytes per
+ * (token, kv head) row instead of 256.  A row's rule is o3v_quantize_rows_fp8's bit for bit: scale = the smallest power of two that
+ * brings the row into +-448 (1.0 for a zero row), codes rounded to nearest even; code * scale is exactly a bf16 value.  NOT vLLM's
+ * per-tensor k_scale / v_scale: parity unpinned against vLLM.
+ *
+ * o3v_kv8_quantize: bf16 Ksrc / Vsrc [heads][S][128] (what prefill wrote) -> slots 0..S-1 of the caches and their scales; slots
+ * S..Tmax-1 are not touched.
+ * o3v_kv8_roundtrip (test support): in place on bf16 caches [heads][Tmax][128], rows slot0 .. slot0+n-1 of every head become
+ * dequant(quant(row)).
+ * o3v_attn_decode_kv8: o3v_attn_decode (matrix-core form, nsplit 1..64, k_lo as there) over the fp8 cache of ONE layer.  Knew / Vnew
+ * bf16 [B][Hkv][128] hold the K/V of the newest key ctx-1: the kernel quantises them, stores codes and scale to slot ctx-1 (exactly
+ * one wave per (b, kv head)) and attends to the dequantised row, so the result is bit-identical to o3v_attn_decode on a bf16 cache
+ * holding dequant of slots < ctx-1 and dequant(quant(Knew / Vnew)) at slot ctx-1.  Bytes and scales of slots >= ctx (slot ctx-1 as
+ * found on entry included) and of keys < k_lo never reach the result.  Error bound: o3v_attn_decode's, on the dequantised values.
+ * O3V_ERR_SHAPE: D != 128 or Hq / Hkv > 8. */
+int o3v_kv8_quantize(const void* Ksrc, const void* Vsrc, void* K8, void* V8, float* Ks, float* Vs, long heads, int S, int Tmax, int D,
+                     o3v_stream_t stream);
+int o3v_kv8_roundtrip(void* Kc, void* Vc, long heads, int Tmax, int slot0, int n, int D, o3v_stream_t stream);
+int o3v_attn_decode_kv8(const void* Q, void* K8, void* V8, float* Ks, float* Vs, const void* Knew, const void* Vnew, void* out,
+                        float* part_o, float* part_ml, const int* k_lo, int B, int Hq, int Hkv, int D, int ctx, int Tmax, int nsplit,
+                        float scale, o3v_stream_t stream);
 
 /* GenerationMixin._sample loop, TF:generation/utils.py:2783-2942, steps [step0, step0+n_steps): sample from
  * st->logits, then (unless it is the globally last step) run one decode forward to refill st->logits. */

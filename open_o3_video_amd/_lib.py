@@ -63,7 +63,8 @@ class DecodeState(C.Structure):
                 ("cur_tok", vp), ("finished", vp), ("out_ids", vp), ("margins", vp), ("eos_ids", vp), ("k_lo", vp),
                 ("row_id", vp), ("part_o", vp), ("part_ml", vp), ("sample_scratch", vp), ("workspace", vp),
                 ("ws_bytes", sz), ("group", i32), ("sync", vp), ("top_k", i32), ("kprefix", vp), ("vprefix", vp),
-                ("prefix_cap", i32), ("rows_per_prompt", i32), ("host_stats", vp), ("flags", i32)]
+                ("prefix_cap", i32), ("rows_per_prompt", i32), ("host_stats", vp), ("flags", i32), ("k8", vp), ("v8", vp),
+                ("k8s", vp), ("v8s", vp)]
 
 
 class LogprobOpts(C.Structure):
@@ -131,6 +132,9 @@ SIGNATURES = {
     "o3v_decode_attn_block": [vp, vp, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32,
                               i32, f32, vp, C.c_uint32, vp],
     "o3v_quantize_rows_fp8": [vp, vp, vp, i32, i32, i32, i32, vp],
+    "o3v_kv8_quantize": [vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, vp],
+    "o3v_kv8_roundtrip": [vp, vp, i64, i32, i32, i32, i32, vp],
+    "o3v_attn_decode_kv8": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, vp],
     "o3v_rmsnorm_quantize_fp8": [vp, vp, vp, vp, i32, i32, i32, i32, f32, vp],
     "o3v_gemm_fp8": [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp],
     "o3v_gemm_fp8_sched": [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp],
@@ -180,8 +184,9 @@ SAMPLE_SCRATCH_FLOATS = 40960   # O3V_SAMPLE_SCRATCH_FLOATS in include/o3v.h
 MAX_LOGPROBS = 20               # O3V_MAX_LOGPROBS
 MAX_COUNT = 65535               # the u16 output counts of o3v_sampling_opts saturate here
 LOGPROB_ROW_SCRATCH_FLOATS = 384  # O3V_LOGPROB_ROW_SCRATCH_FLOATS
-# o3v_decode_state.flags: O3V_DECODE_LAYER_BLOCK, O3V_DECODE_NO_TAIL_NORM, O3V_DECODE_NO_QKV_FUSED_NORM (the last two switch a form OFF)
-DECODE_LAYER_BLOCK, DECODE_NO_TAIL_NORM, DECODE_NO_QKV_FUSED_NORM = 1, 2, 4
+# o3v_decode_state.flags: O3V_DECODE_LAYER_BLOCK, O3V_DECODE_NO_TAIL_NORM, O3V_DECODE_NO_QKV_FUSED_NORM (these two switch a form OFF),
+# O3V_DECODE_KV8_EMULATE (tests: the fp8 K/V arithmetic on a bf16 cache)
+DECODE_LAYER_BLOCK, DECODE_NO_TAIL_NORM, DECODE_NO_QKV_FUSED_NORM, DECODE_KV8_EMULATE = 1, 2, 4, 8
 
 _lib = None
 

@@ -702,6 +702,13 @@ __global__ __launch_bounds__(128) void attn_decode_combine_kernel(const float* _
 
 }  // namespace
 
+// the merge of the context splits at head_dim 128 as a launch of its own, for the decode attention of o3v_kv8.hip
+int o3v_attn_decode_combine128(const float* part_o, const float* part_ml, void* out, int rows, int nsplit, hipStream_t stream) {
+    O3V_KLAUNCH((attn_decode_combine_kernel<128>), dim3(rows), dim3(128), 0, stream, part_o, part_ml, (bf16_t*)out, nsplit);
+    O3V_CHECK_LAUNCH();
+    return O3V_OK;
+}
+
 extern "C" int o3v_attn_tiles_prefix(const void* Q, const void* K, const void* V, const void* Kpre, const void* Vpre, long p_hs,
                                      long p_bs, int prefix_len, int rows_per_prefix, void* O, const int* tiles, int n_tiles,
                                      int rows_per_tile, int Hq, int n_rep, int D, long q_ts, long k_ts, long k_hs, long k_bs,

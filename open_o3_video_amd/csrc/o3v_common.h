@@ -193,3 +193,5 @@ int o3v_sample_top_k_top_p_ex(const void* logits, void* seen, int* cur_tok, int*
                                int top_k, float top_p, uint64_t seed, const int* row_id, int step, int out_stride, float* scratch,
                                uint8_t* seen_prev, const o3v_samp_x* sx, hipStream_t stream);
 // sx (optional, both samplers): the extended controls; the `_x` kernels run the same stages on the extended row
+// o3v_attn.hip: attn_decode_combine_kernel<128> on `rows` = B * Hq (b, head) pairs
+int o3v_attn_decode_combine128(const float* part_o, const float* part_ml, void* out, int rows, int nsplit, hipStream_t stream);

@@ -451,6 +451,7 @@ namespace {
 struct Regime {
     Weights weights, qkv_weights;                     // of the linears; of q/k/v
     bool norm_apart, qkv_fused_norm, qk_norm, group;  // fixed for the call
+    bool kv8, kv8_emulate;                            // fp8 K/V cache; its arithmetic emulated on a bf16 cache (tests)
     bool block, layer_block, tail;                    // tried, may fall back: see settle()
 };
 // The one rule of the try-then-fall-back forms: O3V_ERR_SHAPE from the FIRST launch of a form in a call (layer 0 of its first step)
@@ -491,6 +492,12 @@ Regime decide_regime(const o3v_llm_desc* d, const o3v_decode_state* st) {
     // 8..32 bf16 rows: the residual linears normalise for the linear that follows (o3v_linear_decode_norm_next), so only layer 0's
     // first norm of a step is a launch of its own.  O3V_DECODE_NO_TAIL_NORM switches it off (A/B, tests).
     r.tail = r.norm_apart && !fp8b && st->sync && !(st->flags & O3V_DECODE_NO_TAIL_NORM) && d->lm_head_p && l0.o_wp && l0.down_wp;
+    // fp8 K/V (independent rows only; o3v_llm_decode_ex refuses it for groups): q/k/v writes the new token's bf16 K/V rows into one
+    // layer's worth of staging rows, the attention kernel quantises them into the cache -- stand-alone launches, no one-launch form.
+    // The emulation (tests) round-trips the new token's row of an ordinary bf16 cache after q/k/v instead.
+    r.kv8 = st->k8 != nullptr;
+    r.kv8_emulate = !r.kv8 && (st->flags & O3V_DECODE_KV8_EMULATE);
+    if (r.kv8 || r.kv8_emulate) r.block = r.layer_block = false;
     return r;
 }
 
@@ -513,8 +520,11 @@ struct Decode {
     bool h2_ready;      // w.h holds RMSNorm(x; ln2 of the running layer)
     bool normed_ready;  // w.normed holds RMSNorm(x; final_norm)
     void x_changed() { h_ready = h2_ready = normed_ready = false; }
-    char* kc(int l) const { return (char*)st->kcache + l * layer_stride; }
-    char* vc(int l) const { return (char*)st->vcache + l * layer_stride; }
+    // where q/k/v appends the new token's K/V: slot slot0 + step of layer l's cache; fp8 K/V: the staging rows [B][Hkv][1][D]
+    char* kc(int l) const { return (char*)st->kcache + (r.kv8 ? 0 : l * layer_stride); }
+    char* vc(int l) const { return (char*)st->vcache + (r.kv8 ? 0 : l * layer_stride); }
+    int kv_slot() const { return r.kv8 ? 0 : slot0 + step; }
+    int kv_cap() const { return r.kv8 ? 1 : st->Tmax; }
     uint32_t epoch(int l) const { return (uint32_t)(step * d->layers + l + 1); }  // of the one-launch forms
     bool first(int l) const { return l == 0 && step == step0; }                   // the launch at which settle() may switch a form off
     int sample(const o3v_logprob_opts* lp, const o3v_sampling_opts* so) {
@@ -555,20 +565,27 @@ struct Decode {
         const void *xin = apart ? w.h : st->x, *ln = apart ? nullptr : lw.ln1;  // normalised x, or x and the norm to fuse
         if (r.qk_norm) {
             TRY(lin(wf, xin, ln, lw.qkv_w, lw.qkv_wp, lw.qkv_w8, lw.qkv_w8p, lw.qkv_s, lw.qkv_b, w.qkv, NQKV, H, NQKV, O3V_EPI_NONE));
-            return o3v_qkv_norm_rope_cache(w.qkv, lw.q_norm, lw.k_norm, d->rms_eps, st->cosT, st->sinT, w.q, kc(l), vc(l), slot0 + step, B, 1,
-                                           Hq, Hkv, D, st->Tmax, st->Tnew, step, s);
+            return o3v_qkv_norm_rope_cache(w.qkv, lw.q_norm, lw.k_norm, d->rms_eps, st->cosT, st->sinT, w.q, kc(l), vc(l), kv_slot(), B, 1,
+                                           Hq, Hkv, D, kv_cap(), st->Tnew, step, s);
         }
         if (wf == W_FP8_FRAGS)
-            return o3v_qkv_rope_fp8_rows(w.h, lw.qkv_w8p, lw.qkv_s, lw.qkv_b, B, H, H, st->cosT, st->sinT, w.q, kc(l), vc(l), slot0 + step, Hq,
-                                         Hkv, D, st->Tmax, st->Tnew, step, s);
+            return o3v_qkv_rope_fp8_rows(w.h, lw.qkv_w8p, lw.qkv_s, lw.qkv_b, B, H, H, st->cosT, st->sinT, w.q, kc(l), vc(l), kv_slot(), Hq,
+                                         Hkv, D, kv_cap(), st->Tnew, step, s);
         if (wf == W_FP8_ROWS)
             return o3v_gemv_norm_qkv_rope_fp8(st->x, lw.ln1, d->rms_eps, lw.qkv_w8, lw.qkv_s, lw.qkv_b, B, H, H, st->cosT, st->sinT, w.q,
-                                              kc(l), vc(l), slot0 + step, Hq, Hkv, D, st->Tmax, st->Tnew, step, s);
+                                              kc(l), vc(l), kv_slot(), Hq, Hkv, D, kv_cap(), st->Tnew, step, s);
         return o3v_gemv_norm_qkv_rope(xin, ln, ln ? d->rms_eps : 0.f, lw.qkv_w, lw.qkv_wp, lw.qkv_b, B, H, H, st->cosT, st->sinT, w.q, kc(l),
-                                      vc(l), slot0 + step, Hq, Hkv, D, st->Tmax, st->Tnew, step, s);
+                                      vc(l), kv_slot(), Hq, Hkv, D, kv_cap(), st->Tnew, step, s);
     }
     // attention + merge of layer l on the stand-alone kernels
     int attention(int l) {
+        if (r.kv8) {
+            const size_t rows = (size_t)l * B * Hkv * st->Tmax;  // (token, kv head) rows of the layers before l
+            return o3v_attn_decode_kv8(w.q, (char*)st->k8 + rows * D, (char*)st->v8 + rows * D, st->k8s + rows, st->v8s + rows, st->kcache,
+                                       st->vcache, w.att, st->part_o, st->part_ml, st->k_lo, B, Hq, Hkv, D, st->S + step + 1, st->Tmax,
+                                       st->nsplit, scale, s);
+        }
+        if (r.kv8_emulate) TRY(o3v_kv8_roundtrip(kc(l), vc(l), (long)B * Hkv, st->Tmax, slot0 + step, 1, D, s));
         if (r.group)
             return o3v_attn_decode_group_prefix(w.q, kc(l), vc(l), st->kprefix ? (const char*)st->kprefix + l * pre_stride : nullptr,
                                                 st->kprefix ? (const char*)st->vprefix + l * pre_stride : nullptr, st->prefix_cap,
@@ -668,6 +685,8 @@ extern "C" int o3v_llm_decode_ex(const o3v_llm_desc* d, const o3v_decode_state* 
         return O3V_ERR_ARG;
     if (pfx && (!st->vprefix || st->group <= 1 || st->rows_per_prompt <= 0 || (B % st->rows_per_prompt) || st->S > st->prefix_cap))
         return O3V_ERR_ARG;
+    if (st->k8 && (!st->v8 || !st->k8s || !st->v8s || st->group > 1 || pfx || st->nsplit <= 0)) return O3V_ERR_ARG;
+    if (st->k8 && d->head_dim != 128) return O3V_ERR_SHAPE;
     Decode c{d, st, s, decide_regime(d, st), (long long*)st->host_stats, step0};
     c.B = B, c.H = d->hidden, c.Hq = d->heads, c.Hkv = d->kv_heads, c.D = d->head_dim, c.I = d->inter, c.V = d->vocab;
     c.QD = c.Hq * c.D, c.NQKV = (c.Hq + 2 * c.Hkv) * c.D, c.slot0 = pfx ? 0 : st->S;  // slot0: cache slot of generated token 0

@@ -116,6 +116,14 @@ def plan_decode(num_attention_heads: int, num_key_value_heads: int, head_dim: in
     return DecodePlan(B, own_splits, bool(shared_prompt), Tmax, nsplit, group, want_sync)
 
 
+def kv_cache_in_effect(kv_cache_dtype: str, head_dim: int, plan: DecodePlan) -> str:
+    """The K/V cache format a generate call decodes on: "fp8" iff the engine asks for it (`O3VEngine.kv_cache_dtype`), the kernels
+    exist for the head size (128) and every row streams its own context (`not plan.shared_prompt`); else "bf16".  Shared-prompt
+    groups keep bf16: their prompt K/V is read once per group, so the step is latency-bound there and halving those bytes buys
+    nothing, while the rows' own caches hold only the generated tokens."""
+    return "fp8" if kv_cache_dtype == "fp8" and head_dim == 128 and not plan.shared_prompt else "bf16"
+
+
 def trimmed_length(gen: np.ndarray, eos_ids, ended: dict, done: int) -> int:
     """Columns of gen i64 [B, done] that HF would have produced: up to and including the step at which the last row finished.
     A row finishes at its first id of `eos_ids`, a row the stop checker ended (`ended`: row -> tokens it keeps) at the column the
@@ -162,13 +170,14 @@ class _DecodeBuffers:
     The structs hold bare addresses, so this object lives until the last o3v_llm_decode_ex call and the final check_waits()."""
 
     def __init__(self, eng: "O3VEngine", plan: DecodePlan, S, T, G, ids_rep, pad_rep, eos_token_ids, row_ids, return_margins, n_lp,
-                 sampling, knobs, cosd, sind, logits, kc, vc, kc0, vc0):
+                 sampling, knobs, cosd, sind, logits, kc, vc, kc0, vc0, kv8=None, kv8_emulate=False):
         tc, dev = eng.cfg.text, eng.dev
         B, V = plan.B, tc.vocab_size
         zeros = lambda shape, dtype: torch.zeros(shape, dtype=dtype, device=dev)
         empty = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=dev)
         addr = lambda t: 0 if t is None else t.data_ptr()
-        self.caches, self.tables, self.logits = (kc, vc, kc0, vc0), (cosd, sind), logits
+        # kv8 = (k8, v8, k8s, v8s): the fp8 K/V caches; kc / vc are then the bf16 staging rows [B, Hkv, 1, D] of the new token
+        self.caches, self.tables, self.logits = (kc, vc, kc0, vc0, kv8), (cosd, sind), logits
         self.seen = zeros((B, V), torch.uint8)
         if knobs["rep_penalty"] != 1.0:
             ids_dev = torch.from_numpy(ids_rep.astype(np.int32)).to(dev)
@@ -219,7 +228,9 @@ class _DecodeBuffers:
         self.host_stats = (C.c_longlong * 4)(0, 0, 0, 0)
         self.st.host_stats = C.cast(self.host_stats, C.c_void_p)
         self.st.flags = ((_lib.DECODE_LAYER_BLOCK if eng.layer_block else 0) | (0 if eng.tail_norm else _lib.DECODE_NO_TAIL_NORM) |
-                         (0 if eng.qkv_fused_norm else _lib.DECODE_NO_QKV_FUSED_NORM))
+                         (0 if eng.qkv_fused_norm else _lib.DECODE_NO_QKV_FUSED_NORM) | (_lib.DECODE_KV8_EMULATE if kv8_emulate else 0))
+        if kv8 is not None:
+            self.st.k8, self.st.v8, self.st.k8s, self.st.v8s = (t.data_ptr() for t in kv8)
 
     def check_waits(self):
         """Reads the sticky time-out word of the in-launch waits (a device-to-host copy); raises if one of them gave up."""
@@ -282,6 +293,9 @@ class O3VEngine:
         # opt-in (BASELINE config #5): the LLM prefill / log-prob linears as fp8 x fp8 on the matrix cores (W8A8: per-token activation
         # scales, the fp8 rows + per-row scales that fp8_decode builds).  Off by default: the bf16 path and its goldens are untouched.
         self.fp8_prefill = False
+        # opt-in (vLLM kv_cache_dtype): "fp8" keeps the K/V cache of independent-row decodes as e4m3fn rows with one power-of-two
+        # scale per (token, kv head) -- 132 instead of 256 bytes per row; see kv_cache_in_effect for where it applies.  "bf16": off.
+        self.kv_cache_dtype = "bf16"
 
     # ------------------------------------------------------------------------------------------ vision
     def _vit_plan(self, grid_thw):
@@ -631,9 +645,19 @@ class O3VEngine:
         sampling = self._sampling_vectors(tc.vocab_size, T, eos_token_ids, bool(do_sample), min_p, presence_penalty, frequency_penalty,
                                           min_new_tokens, token_bias, allowed_token_ids, banned_token_ids)
         nsplit_env = os.environ.get("O3V_NSPLIT")      # A/B switch (tools/probes), read at every call
-        plan = plan_decode(tc.num_attention_heads, tc.num_key_value_heads, tc.head_dim, B0, G, S, T, self.group_attention,
-                           self.group_attention_mode, self.fused_decode and _fused_ok, self.tail_norm,
-                           int(nsplit_env) if nsplit_env else None)
+        if self.kv_cache_dtype not in ("bf16", "fp8"):
+            raise ValueError(f"kv_cache_dtype={self.kv_cache_dtype!r}: 'bf16' or 'fp8'")
+
+        def make_plan(fused):
+            return plan_decode(tc.num_attention_heads, tc.num_key_value_heads, tc.head_dim, B0, G, S, T, self.group_attention,
+                               self.group_attention_mode, fused, self.tail_norm, int(nsplit_env) if nsplit_env else None)
+
+        plan = make_plan(self.fused_decode and _fused_ok)
+        # fp8 K/V (or, test hook, its arithmetic emulated on bf16 caches): the stand-alone attention kernels, so no hand-off buffer
+        emulate = bool(getattr(self, "_debug_kv8_emulate", False)) and kv_cache_in_effect("fp8", tc.head_dim, plan) == "fp8"
+        kv_dtype = "bf16" if emulate else kv_cache_in_effect(self.kv_cache_dtype, tc.head_dim, plan)
+        if kv_dtype == "fp8" or emulate:
+            plan = make_plan(False)
         B = plan.B
         tm = {}
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)] if sync_timings else None
@@ -650,7 +674,8 @@ class O3VEngine:
         mark(1)
         # ---- positions + prefill (once per prompt); a call asking for prompt log-probs neither reuses nor stores prefix K/V
         pos, deltas = self._positions(ids, mask, grid, vgrid, second_per_grid_ts)
-        x, kc, vc, kc0, vc0, past = self._prefill_prompt(ids, pad, pos, vis, n_img_rows, G, plan, None if n_plp else prefix_key)
+        x, kc, vc, kc0, vc0, past, kv8 = self._prefill_prompt(ids, pad, pos, vis, n_img_rows, G, plan, None if n_plp else prefix_key,
+                                                              kv_dtype == "fp8", emulate)
         tm["prefix_tokens_reused"] = past
         self._last_prompt = None
         if self.reuse_prompt_kv and plan.shared_prompt and B0 == 1:
@@ -672,8 +697,10 @@ class O3VEngine:
         knobs = dict(pad_id=pad_id, n_eos=len(eos_token_ids), do_sample=int(do_sample), rep_penalty=float(repetition_penalty),
                      temperature=float(temperature), top_p=float(top_p), seed=int(seed) & (2 ** 64 - 1), top_k=max(0, int(top_k or 0)))
         buf = _DecodeBuffers(self, plan, S, T, G, ids_rep, np.repeat(pad, G) if G > 1 else pad, eos_token_ids, row_ids, return_margins,
-                             n_lp, sampling, knobs, cosd, sind, logits, kc, vc, kc0, vc0)
-        tm["kv_cache_bytes"] = int((kc.numel() + vc.numel() + (kc0.numel() + vc0.numel() if plan.shared_prompt else 0)) * 2)
+                             n_lp, sampling, knobs, cosd, sind, logits, kc, vc, kc0, vc0, kv8, emulate)
+        tm["kv_cache_dtype"] = kv_dtype
+        tm["kv_cache_bytes"] = int((kc.numel() + vc.numel() + (kc0.numel() + vc0.numel() if plan.shared_prompt else 0)) * 2 +
+                                   sum(t.numel() * t.element_size() for t in kv8 or ()))
         use_eos = len(eos_token_ids) > 0
         done, ended = self._decode_loop(buf, T, use_eos, steps_per_sync, stop_checker)
         mark(3)
@@ -685,7 +712,8 @@ class O3VEngine:
         buf.check_waits()
         if getattr(self, "_debug_keep", False):     # probe hook: the decode's state after the last step
             self._debug_last = {"kc": kc, "vc": vc, "logits": logits, "x": buf.x, "S": S, "cos": cosd, "sin": sind, "k_lo": buf.k_lo,
-                                "nsplit": plan.nsplit, "Tmax": plan.Tmax, "out_ids": buf.out_ids}
+                                "nsplit": plan.nsplit, "Tmax": plan.Tmax, "out_ids": buf.out_ids,
+                                **dict(zip(("k8", "v8", "k8s", "v8s"), kv8 or (None,) * 4))}
         gen = buf.out_ids[:, :done].to(torch.int64)
         if use_eos or ended:
             # HF stops at the step where every row has finished: trim trailing all-pad columns generated past it
@@ -702,12 +730,19 @@ class O3VEngine:
         return GenerateOutput(sequences=seqs, margins=None if margins is None else margins[:, :done], n_steps=done,
                               timings=tm, logprobs=lp, prompt_logprobs=plp)
 
-    def _prefill_prompt(self, ids, pad, pos, vis, n_img_rows, G, plan: DecodePlan, prefix_key):
+    def _prefill_prompt(self, ids, pad, pos, vis, n_img_rows, G, plan: DecodePlan, prefix_key, kv8: bool = False,
+                        kv8_emulate: bool = False):
         """The prompt stage of generate: the caches, the tokens whose K/V are kept under `prefix_key` (single un-padded prompt)
         copied in, the prefill of the rest, the fan-out to the G rows of each prompt, the prefix store.
         -> (x: last-layer rows of the tokens run [B0 * (S - past), H], kc, vc: the decode caches, kc0, vc0: the prompt's K/V kept
-        once (None unless plan.shared_prompt), past: tokens reused)."""
+        once (None unless plan.shared_prompt), past: tokens reused, kv8: None or the fp8 caches (k8, v8, k8s, v8s)).
+        kv8 (never with plan.shared_prompt): the prompt is prefilled in bf16 into an entry of S slots -- prefill attention itself
+        runs on unquantised K/V -- and quantised from there into fp8 caches of plan.Tmax slots; the entry is released (the
+        `prefix_key` store keeps its bf16 copy) and kc / vc are the staging rows of the new token [B, Hkv, 1, D].
+        kv8_emulate (test hook): bf16 caches whose prompt slots are replaced by dequant(quant(row))."""
         B0, S = ids.shape
+        if kv8:
+            return self._prefill_prompt_kv8(ids, pad, pos, vis, n_img_rows, G, plan, prefix_key)
         kc, vc = self.alloc_cache(plan.B, plan.Tmax)
         kc0 = vc0 = None
         past = 0
@@ -735,7 +770,47 @@ class O3VEngine:
                 self._prefix_store(prefix_key, ids[0], kc0, vc0)
             if not plan.shared_prompt:
                 kc0 = vc0 = None
-        return x, kc, vc, kc0, vc0, past
+        if kv8_emulate:
+            _lib.call("o3v_kv8_roundtrip", _ptr(kc), _ptr(vc), kc.shape[0] * kc.shape[1] * kc.shape[2], plan.Tmax, 0, S, kc.shape[4],
+                      _stream())
+        return x, kc, vc, kc0, vc0, past, None
+
+    def _prefill_prompt_kv8(self, ids, pad, pos, vis, n_img_rows, G, plan: DecodePlan, prefix_key):
+        tc = self.cfg.text
+        B0, S = ids.shape
+        L, Hkv, D = tc.num_hidden_layers, tc.num_key_value_heads, tc.head_dim
+        past = 0
+        use_prefix = prefix_key is not None and B0 == 1 and int(pad[0]) == 0
+        if use_prefix:
+            past = self._prefix_lookup(prefix_key, ids[0])
+        x = self.embed(ids, vis, first=past, n_image_rows=n_img_rows)
+        kc0, vc0 = self.alloc_cache(B0, S)
+        if past:
+            ent = self._prefix[prefix_key]
+            kc0[:, :, :, :past].copy_(ent["k"][:, :, :, :past])
+            vc0[:, :, :, :past].copy_(ent["v"][:, :, :, :past])
+        self.prefill(x, pos[:, :, past:], pad, B0, S - past, kc0, vc0, past=past, deepstack=(ids, vis) if self.q3 else None)
+        if use_prefix:
+            self._prefix_store(prefix_key, ids[0], kc0, vc0)
+
+        def caches(rows, slots):
+            return tuple(torch.empty((L, rows, Hkv, slots) + tail, dtype=dt, device=self.dev)
+                         for tail, dt in (((D,), torch.uint8), ((D,), torch.uint8), ((), torch.float32), ((), torch.float32)))
+
+        def quantize(dst, slots):
+            _lib.call("o3v_kv8_quantize", _ptr(kc0), _ptr(vc0), *(_ptr(t) for t in dst), L * B0 * Hkv, S, slots, D, _stream())
+
+        kv8 = caches(plan.B, plan.Tmax)
+        if G == 1:
+            quantize(kv8, plan.Tmax)
+        else:
+            # KV fan-out of the quantised prompt: completion g of prompt b is row b*G+g (the broadcast copy of the bf16 path)
+            once = caches(B0, S)
+            quantize(once, S)
+            for dst, src in zip(kv8, once):
+                dst.view((L, B0, G) + tuple(dst.shape[2:]))[:, :, :, :, :S].copy_(src[:, :, None])
+        kc, vc = (torch.empty((plan.B, Hkv, 1, D), dtype=torch.bfloat16, device=self.dev) for _ in range(2))
+        return x, kc, vc, None, None, past, kv8
 
     def _decode_loop(self, buf: "_DecodeBuffers", T: int, use_eos: bool, steps_per_sync: int, stop_checker):
         """Chunks of decode steps enqueued from C++, one host check per chunk (TF:utils.py:2936-2937) -> (steps done, ended: rows

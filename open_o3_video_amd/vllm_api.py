@@ -207,7 +207,12 @@ class LLM:
                  max_num_seqs: int = 8, engine: Optional[O3VEngine] = None, tokenizer: Any = None,
                  min_pixels: int = 56 * 56, max_pixels: int = 14 * 14 * 4 * 1280, device="cuda",
                  enable_prefix_caching: bool = True, quantization: Optional[str] = None, mm_processor_kwargs: Optional[dict] = None,
-                 position_mode: str = "pinned", fp8_prefill: bool = False, **_):
+                 position_mode: str = "pinned", fp8_prefill: bool = False, kv_cache_dtype: str = "auto", **_):
+        # vLLM's keyword: "fp8" / "fp8_e4m3" keep the K/V cache of independent-row decodes as e4m3fn rows with one power-of-two scale
+        # per (token, kv head) (O3VEngine.kv_cache_dtype; not vLLM's per-tensor k_scale / v_scale: parity unpinned against vLLM)
+        kv_dtypes = {"auto": "bf16", "bfloat16": "bf16", "fp8": "fp8", "fp8_e4m3": "fp8"}
+        if kv_cache_dtype not in kv_dtypes:
+            raise ValueError(f"kv_cache_dtype={kv_cache_dtype!r}: only 'auto', 'bfloat16', 'fp8' or 'fp8_e4m3' is built")
         if tensor_parallel_size != 1:
             raise ValueError("the reference runs tensor_parallel_size=1 (R:eval/models/model_vllm.py:21); data parallelism "
                              "is one engine per GPU (open_o3_video_amd.dist)")
@@ -245,6 +250,7 @@ class LLM:
             ge = load_generation_config(model).get("eos_token_id")
             self.generation_eos_ids = [] if ge is None else ([int(e) for e in ge] if isinstance(ge, (list, tuple)) else [int(ge)])
         self.engine, self.tokenizer = engine, tokenizer
+        engine.kv_cache_dtype = kv_dtypes[kv_cache_dtype]
         self.image_factor = engine.cfg.vision.patch_size * engine.cfg.vision.spatial_merge_size   # 28; Qwen3-VL: 32
         self.max_num_seqs = int(max_num_seqs)   # requests of one generate() call decoded together (<= O3VEngine.MAX_ROWS)
         self.cfg = engine.cfg
