@@ -178,7 +178,8 @@ int o3v_gemv_norm_qkv_rope_fp8(const void* X, const void* norm_w, float eps, con
                                int cs_off, o3v_stream_t stream);
 
 /* ---- attention ---------------------------------------------------------------------------------------------- */
-/* tiles: int32[n_tiles][8] = {q_row0, q_rows (<= rows_per_tile), k_row0, k_len, causal_off, k_lo, batch, 0};
+/* tiles: int32[n_tiles][8] = {q_row0, q_rows (<= rows_per_tile), k_row0, k_len, causal_off, k_lo, batch, own_lo};
+ * word 7 is read by o3v_attn_tiles_prefix with a prompt entry only (see there) and is 0 everywhere else;
  * rows_per_tile 64 (ragged ViT windows) or 128 (prefill).
  * ViT varlen attention (TF:248-287) and causal GQA prefill attention (TF:186-208, :602-689).
  * Rounding points (u = 2^-8, the bf16 unit roundoff; p_j the exact softmax weights, ref = sum_j p_j v_j): scores, running
@@ -193,7 +194,10 @@ int o3v_attn_tiles(const void* Q, const void* K, const void* V, void* O, const i
                    long o_ts, float scale, o3v_stream_t stream);
 /* The same with a shared prompt entry: keys 0..prefix_len-1 of a tile come from Kpre / Vpre ([batch / rows_per_prefix] at
  * stride p_bs, kv head at stride p_hs, token strides k_ts / v_ts), later keys from K / V whose rows then start at logical key
- * prefix_len -- the completions of one prompt run behind ONE copy of its K/V (R:grpo_trainer.py:601-632 log-prob pass). */
+ * prefix_len -- the completions of one prompt run behind ONE copy of its K/V (R:grpo_trainer.py:601-632 log-prob pass).
+ * Descriptor word 7 (Kpre != NULL only): own_lo of the tile's batch row.  The first own_lo rows of K / V are the left padding of a
+ * suffix behind the shared prefix, so the logical keys prefix_len .. prefix_len + own_lo - 1 are masked for every query row of
+ * the tile (they hold finite values; k_lo still counts the padding in FRONT of the prefix).  0: no gap, the bits of before. */
 int o3v_attn_tiles_prefix(const void* Q, const void* K, const void* V, const void* Kpre, const void* Vpre, long p_hs, long p_bs,
                           int prefix_len, int rows_per_prefix, void* O, const int* tiles, int n_tiles, int rows_per_tile, int Hq,
                           int n_rep, int D, long q_ts, long k_ts, long k_hs, long k_bs, long v_ts, long v_hs, long v_bs, long o_ts,
@@ -217,6 +221,16 @@ int o3v_attn_decode_group_prefix(const void* Q, const void* Kc, const void* Vc, 
                                  int rows_per_prompt, void* out, float* part_o, float* part_ml, const int* k_lo, int B, int G,
                                  int Hq, int Hkv, int D, int prefix_len, int ctx, int Tmax, int nsplit_prefix, float scale,
                                  o3v_stream_t stream);
+/* The same for rows that share a prefix and continue with suffixes of their own length ("one video, several questions"): the
+ * suffixes sit LEFT-PADDED in the rows' own caches, so that every row's newest token lands in the same slot.  own_lo [B] (needs
+ * Kpre / Vpre): row b's slots 0 .. own_lo[b]-1 are that padding, i.e. its logical keys prefix_len .. prefix_len + own_lo[b] - 1
+ * are masked: visible are [k_lo, prefix_len) and [prefix_len + own_lo[b], ctx).  The padding slots hold finite values (the suffix
+ * prefill wrote them); the kernels may read them and mask them.  own_lo == NULL: exactly o3v_attn_decode_group_prefix.  In the
+ * shared-read form (nsplit_prefix < 0) with a prompt entry G = 1 is valid too: no row reads another row's cache there. */
+int o3v_attn_decode_group_prefix_lo(const void* Q, const void* Kc, const void* Vc, const void* Kpre, const void* Vpre, int prefix_cap,
+                                    int rows_per_prompt, void* out, float* part_o, float* part_ml, const int* k_lo, const int* own_lo,
+                                    int B, int G, int Hq, int Hkv, int D, int prefix_len, int ctx, int Tmax, int nsplit_prefix,
+                                    float scale, o3v_stream_t stream);
 
 /* One launch for the attention half of a batch-1 decode layer (TF:692-757 first half; replaces o3v_gemv_norm_qkv_rope +
  * o3v_attn_decode + o3v_linear_decode(o_proj, RESIDUAL), bit-identical to them): the three stages are roles of the
@@ -486,7 +500,8 @@ int o3v_llm_prefill(const o3v_llm_desc* d, void* x, const void* cosT, const void
  *  * shared prompt entry: the first prefix_len of the `past` tokens of every row live ONCE per prompt in kprefix / vprefix
  *    ([layers][B / rows_per_prefix][Hkv][prefix_cap][D]); kcache / vcache [layers][B][Hkv][Tmax][D] then hold only the tokens
  *    behind them (this call's S tokens land in slots past - prefix_len ..) -- the G completions of one prompt run behind one
- *    copy of its K/V (R:grpo_trainer.py:601-632).  Tile descriptors keep logical key indexes (k_len = past + S).
+ *    copy of its K/V (R:grpo_trainer.py:601-632).  Tile descriptors keep logical key indexes (k_len = past + S); their word 7 is
+ *    own_lo of the batch row: that many of the row's first own slots are left padding and masked (o3v_attn_tiles_prefix).
  *  * w8a8 (BASELINE config #5, "fp8 weights on CDNA4 fp8 MFMA"): 1 = run the four linears of every layer as fp8 x fp8 on the matrix
  *    cores (o3v_gemm_fp8: per-token activation scales, the per-row weight scales of the fp8 rows) when the descriptor carries fp8
  *    rows and the widths are whole 128-byte k-tiles, else the bf16 path; 2 = the same but O3V_ERR_SHAPE instead of the bf16 path. */
@@ -551,6 +566,13 @@ typedef struct {
      * S + step.  The attention half runs on the stand-alone kernels (no one-launch block at B = 1).  NULL: off. */
     void *k8, *v8;
     float *k8s, *v8s;
+    /* optional suffixes behind a shared prefix (both need kprefix, group > 1 and no fp8 K/V; anything else is O3V_ERR_ARG before any
+     * launch).  own_past: every row's own cache already holds this many slots -- the rows' suffixes, left-padded to one length --
+     * so generated token `step` goes to slot own_past + step, ctx = S + own_past + step + 1, prefix_len = S and Tmax >= own_past +
+     * Tnew - 1.  own_lo [B]: the padding slots at the start of each row's own cache (o3v_attn_decode_group_prefix_lo), NULL = none.
+     * A zeroed pair is the behaviour of before. */
+    int own_past;
+    const int* own_lo;
 } o3v_decode_state;
 /* o3v_decode_state.flags.  LAYER_BLOCK: batch-1 bf16 decode may use the persistent layer block (o3v_decode_layer_block) where its
  * shapes allow, then one launch for the attention half + gate/up and one for down_proj per layer; otherwise o3v_decode_attn_block +

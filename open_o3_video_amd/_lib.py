@@ -67,6 +67,12 @@ class DecodeState(C.Structure):
                 ("k8s", vp), ("v8s", vp)]
 
 
+class DecodeStateOwn(DecodeState):
+    """The whole o3v_decode_state: DecodeState (the fields up to `v8s`) followed by the pair of the suffixes behind a shared prefix.
+    The decode entry points read the pair, so they take this type only."""
+    _fields_ = [("own_past", i32), ("own_lo", vp)]
+
+
 class LogprobOpts(C.Structure):
     _fields_ = [("n", i32), ("chosen_lp", vp), ("chosen_rank", vp), ("top_ids", vp), ("top_lp", vp)]
 
@@ -164,16 +170,18 @@ SIGNATURES = {
     "o3v_attn_tiles_prefix": [vp, vp, vp, vp, vp, i64, i64, i32, i32, vp, vp, i32, i32, i32, i32, i32, i64, i64, i64, i64, i64, i64, i64,
                               i64, f32, vp],
     "o3v_attn_decode_group_prefix": [vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, f32, vp],
+    "o3v_attn_decode_group_prefix_lo": [vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32,
+                                        f32, vp],
     "o3v_llm_head": [C.POINTER(LlmDesc), vp, i32, i32, vp, vp, vp],
-    "o3v_llm_decode": [C.POINTER(LlmDesc), C.POINTER(DecodeState), i32, i32, i32, vp],
+    "o3v_llm_decode": [C.POINTER(LlmDesc), C.POINTER(DecodeStateOwn), i32, i32, i32, vp],
     "o3v_sample_logprobs": [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, f32, i32, f32, u64, vp, i32, i32, vp,
                             C.POINTER(LogprobOpts), vp],
     "o3v_logprobs_rows": [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp],
-    "o3v_llm_decode_lp": [C.POINTER(LlmDesc), C.POINTER(DecodeState), C.POINTER(LogprobOpts), i32, i32, i32, vp],
+    "o3v_llm_decode_lp": [C.POINTER(LlmDesc), C.POINTER(DecodeStateOwn), C.POINTER(LogprobOpts), i32, i32, i32, vp],
     "o3v_repack_rows": [C.POINTER(RepackDesc), vp],
     "o3v_sample_step_ex": [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, f32, i32, f32, u64, vp, i32, i32, vp,
                            C.POINTER(LogprobOpts), C.POINTER(SamplingOpts), vp],
-    "o3v_llm_decode_ex": [C.POINTER(LlmDesc), C.POINTER(DecodeState), C.POINTER(LogprobOpts), C.POINTER(SamplingOpts), i32, i32, i32,
+    "o3v_llm_decode_ex": [C.POINTER(LlmDesc), C.POINTER(DecodeStateOwn), C.POINTER(LogprobOpts), C.POINTER(SamplingOpts), i32, i32, i32,
                           vp],
 }
 _RET = {"o3v_ctx_create": vp, "o3v_ctx_destroy": None, "o3v_ctx_llm": C.POINTER(LlmDesc), "o3v_ctx_vit": C.POINTER(VitDesc),

@@ -29,7 +29,8 @@ struct TileDesc {  // 8 ints, built on the host (open_o3_video_amd/indexing.py)
     int causal_off;  // >= 0: key j allowed iff j <= causal_off + row_in_tile ; < 0: no causal mask
     int k_lo;        // first valid key (left padding)
     int batch;       // batch row (selects the K/V batch stride)
-    int pad_;
+    int pad_;        // PFX kernels: own_lo of the batch row -- keys P .. P + own_lo - 1 are masked (the left padding of a suffix behind
+                     // the shared prefix); 0 = no gap.  Ignored by the non-PFX kernels (every table sets 0 there).
 };
 
 template <int D>
@@ -118,8 +119,10 @@ __global__ __launch_bounds__(256, 2) void attn_tiles_kernel(const bf16_t* __rest
         const int lim = td.causal_off + td.q_rows;  // exclusive
         k_end = lim < k_end ? lim : k_end;
     }
-    const int kt_lo = td.k_lo >> 6;
+    const int kt_lo = td.k_lo >> 6;  // (k_lo counts the padding in front of the prefix, so the prefix tiles are never skipped for a gap)
     const int kt_hi = (k_end + 63) >> 6;
+    // PFX: the gap [P, gap_hi) between the shared prefix and the row's left-padded suffix; empty when word 7 is 0
+    const int gap_hi = PFX ? P + td.pad_ : 0;
 
     // K/V staging.  A split form (global loads of tile kt+1 issued right after the barrier that publishes tile kt, written
     // to LDS after the next barrier) is kept behind SPLIT: it costs 32 VGPRs and with them a block of occupancy, which
@@ -226,7 +229,8 @@ __global__ __launch_bounds__(256, 2) void attn_tiles_kernel(const bf16_t* __rest
         // causal diagonal of this wave, the ragged tail); interior tiles take the mask-free path (wave-uniform branch).
         bf16x8 pb[RQ][2];
         const bool boundary = (kt * 64 < td.k_lo) || (kt * 64 + 63 >= td.k_len) ||
-                              (td.causal_off >= 0 && kt * 64 + 63 > td.causal_off + wave * RQ * 16);
+                              (td.causal_off >= 0 && kt * 64 + 63 > td.causal_off + wave * RQ * 16) ||
+                              (PFX && kt * 64 < gap_hi && kt * 64 + 63 >= P && gap_hi > P);
 #pragma unroll
         for (int rq = 0; rq < RQ; ++rq) {
             float mx = -1e30f;
@@ -238,6 +242,7 @@ __global__ __launch_bounds__(256, 2) void attn_tiles_kernel(const bf16_t* __rest
                         const int j = kt * 64 + kb * 16 + fg * 4 + r;
                         bool v = (j < td.k_len) && (j >= td.k_lo);
                         if (td.causal_off >= 0) v = v && (j <= td.causal_off + qrow_in[rq]);
+                        if (PFX) v = v && !(j >= P && j < gap_hi);
                         s[rq][kb][r] = v ? s[rq][kb][r] : -1e30f;
                         mx = fmaxf(mx, s[rq][kb][r]);
                     }
@@ -472,6 +477,18 @@ __global__ __launch_bounds__(256) void attn_decode_mfma_kernel(const bf16_t* __r
     attn_decode_mfma_body<false>(Q, Kc, Vc, part_o, part_ml, k_lo_arr, ctx, Hq, Hkv, n_rep, k_hs, k_bs, scale_log2e, kbeg,
                                  nsplit_tot, split_off, G, P, blockIdx.x, gridDim.x, blockIdx.y, blockIdx.z, smem, AttnHandoff{}, pf);
 }
+// the same with the gap mask of a shared prefix followed by left-padded suffixes (own_lo_arr, see attn_decode_mfma_body)
+__global__ __launch_bounds__(256) void attn_decode_mfma_gap_kernel(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ Kc,
+                                                                   const bf16_t* __restrict__ Vc, float* __restrict__ part_o,
+                                                                   float* __restrict__ part_ml, const int* __restrict__ k_lo_arr,
+                                                                   const int* __restrict__ own_lo_arr, int ctx, int Hq, int Hkv,
+                                                                   int n_rep, long k_hs, long k_bs, float scale_log2e, int kbeg,
+                                                                   int nsplit_tot, int split_off, int G, int P, PrefixRef pf) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    attn_decode_mfma_body<false, true>(Q, Kc, Vc, part_o, part_ml, k_lo_arr, ctx, Hq, Hkv, n_rep, k_hs, k_bs, scale_log2e, kbeg,
+                                       nsplit_tot, split_off, G, P, blockIdx.x, gridDim.x, blockIdx.y, blockIdx.z, smem, AttnHandoff{},
+                                       pf, own_lo_arr);
+}
 
 // ------------------------------------------------------------------------------------------------
 // Group decode attention over a SHARED prompt prefix (head_dim 128).  The G completions of one prompt
@@ -661,13 +678,14 @@ __device__ __forceinline__ void attn_decode_group_body(const bf16_t* __restrict_
 
 // One launch for a decode step's group attention: blocks [0, n_prefix) run the shared-prefix role for (split, kv head,
 // sub-group), the rest the own-keys role for (split, kv head, row) -- both only write partials, the combine follows.
-template <int NQB>
+// GAP: the own-keys role masks each row's padding slots (own_lo_arr); the prefix role reads only keys below P and needs nothing.
+template <int NQB, bool GAP = false>
 __global__ __launch_bounds__(256) void attn_decode_group_kernel(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ Kc,
                                                                 const bf16_t* __restrict__ Vc, float* __restrict__ part_o,
                                                                 float* __restrict__ part_ml, const int* __restrict__ k_lo_arr,
                                                                 int P, int G, int ctx, int Hq, int Hkv, int n_rep, long k_hs,
                                                                 long k_bs, float scale_log2e, int nsplit_prefix, int nsplit_own,
-                                                                int n_prefix, PrefixRef pf) {
+                                                                int n_prefix, PrefixRef pf, const int* __restrict__ own_lo_arr) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int nsplit_tot = nsplit_prefix + nsplit_own;
     int L = blockIdx.x;
@@ -677,9 +695,9 @@ __global__ __launch_bounds__(256) void attn_decode_group_kernel(const bf16_t* __
     } else {
         L -= n_prefix;
         // own keys P..ctx-1 (with a shared prompt entry the row's cache starts at logical key P: the body offsets it by its P)
-        attn_decode_mfma_body<false>(Q, Kc, Vc, part_o, part_ml, k_lo_arr, ctx, Hq, Hkv, n_rep, k_hs, k_bs, scale_log2e, P,
-                                     nsplit_tot, nsplit_prefix, 1, pf.K ? P : 0, L % nsplit_own, nsplit_own, (L / nsplit_own) % Hkv,
-                                     L / (nsplit_own * Hkv), smem, AttnHandoff{}, pf);
+        attn_decode_mfma_body<false, GAP>(Q, Kc, Vc, part_o, part_ml, k_lo_arr, ctx, Hq, Hkv, n_rep, k_hs, k_bs, scale_log2e, P,
+                                          nsplit_tot, nsplit_prefix, 1, pf.K ? P : 0, L % nsplit_own, nsplit_own,
+                                          (L / nsplit_own) % Hkv, L / (nsplit_own * Hkv), smem, AttnHandoff{}, pf, own_lo_arr);
     }
 }
 
@@ -717,6 +735,10 @@ extern "C" int o3v_attn_decode_group_prefix(const void* Q, const void* Kc, const
                                             int prefix_cap, int rows_per_prompt, void* out, float* part_o, float* part_ml,
                                             const int* k_lo, int B, int G, int Hq, int Hkv, int D, int prefix_len, int ctx, int Tmax,
                                             int nsplit_prefix, float scale, hipStream_t stream);
+extern "C" int o3v_attn_decode_group_prefix_lo(const void* Q, const void* Kc, const void* Vc, const void* Kpre, const void* Vpre,
+                                               int prefix_cap, int rows_per_prompt, void* out, float* part_o, float* part_ml,
+                                               const int* k_lo, const int* own_lo, int B, int G, int Hq, int Hkv, int D, int prefix_len,
+                                               int ctx, int Tmax, int nsplit_prefix, float scale, hipStream_t stream);
 
 extern "C" int o3v_attn_tiles(const void* Q, const void* K, const void* V, void* O, const int* tiles, int n_tiles,
                               int rows_per_tile, int Hq, int n_rep, int D, long q_ts, long k_ts, long k_hs, long k_bs,
@@ -827,8 +849,21 @@ extern "C" int o3v_attn_decode_group_prefix(const void* Q, const void* Kc, const
                                             int prefix_cap, int rows_per_prompt, void* out, float* part_o, float* part_ml,
                                             const int* k_lo, int B, int G, int Hq, int Hkv, int D, int prefix_len, int ctx, int Tmax,
                                             int nsplit_prefix, float scale, hipStream_t stream) {
-    if (!Q || !Kc || !Vc || !out || !part_o || !part_ml || B <= 0 || G <= 1 || (B % G) || Hq <= 0 || Hkv <= 0 || (Hq % Hkv) ||
-        prefix_len <= 0 || ctx <= prefix_len || nsplit_prefix == 0 || (Kpre == nullptr) != (Vpre == nullptr))
+    return o3v_attn_decode_group_prefix_lo(Q, Kc, Vc, Kpre, Vpre, prefix_cap, rows_per_prompt, out, part_o, part_ml, k_lo, nullptr, B, G,
+                                           Hq, Hkv, D, prefix_len, ctx, Tmax, nsplit_prefix, scale, stream);
+}
+
+// own_lo != NULL (needs Kpre / Vpre): row b's own cache starts with own_lo[b] padding slots -- the left padding of a suffix of its
+// own behind the shared prefix -- i.e. the logical keys prefix_len .. prefix_len + own_lo[b] - 1 are masked.  The slots hold finite
+// values (the suffix prefill wrote them).  NULL: no gap, the launches of o3v_attn_decode_group_prefix.  With a prompt entry the
+// shared-read form (nsplit_prefix < 0) never reads another row's cache, so there G = 1 is valid as well.
+extern "C" int o3v_attn_decode_group_prefix_lo(const void* Q, const void* Kc, const void* Vc, const void* Kpre, const void* Vpre,
+                                               int prefix_cap, int rows_per_prompt, void* out, float* part_o, float* part_ml,
+                                               const int* k_lo, const int* own_lo, int B, int G, int Hq, int Hkv, int D, int prefix_len,
+                                               int ctx, int Tmax, int nsplit_prefix, float scale, hipStream_t stream) {
+    const int g_min = (Kpre && nsplit_prefix < 0) ? 1 : 2;
+    if (!Q || !Kc || !Vc || !out || !part_o || !part_ml || B <= 0 || G < g_min || (B % G) || Hq <= 0 || Hkv <= 0 || (Hq % Hkv) ||
+        prefix_len <= 0 || ctx <= prefix_len || nsplit_prefix == 0 || (Kpre == nullptr) != (Vpre == nullptr) || (own_lo && !Kpre))
         return O3V_ERR_ARG;
     if (Kpre ? (ctx - prefix_len > Tmax || prefix_len > prefix_cap || rows_per_prompt <= 0 || (rows_per_prompt % G) || (B % rows_per_prompt))
              : ctx > Tmax)
@@ -842,9 +877,14 @@ extern "C" int o3v_attn_decode_group_prefix(const void* Q, const void* Kc, const
         // shared-read form: the per-row kernel, with every row of a group reading the prefix from the group's first row
         const int ns = -nsplit_prefix;
         if (ns > 64) return O3V_ERR_ARG;
-        O3V_KLAUNCH(attn_decode_mfma_kernel, dim3(ns, Hkv, B), dim3(256), 4 * 32 * 288, stream, (const bf16_t*)Q, (const bf16_t*)Kc,
-                    (const bf16_t*)Vc, part_o, part_ml, k_lo, ctx, Hq, Hkv, n_rep, (long)Tmax * D, (long)Hkv * Tmax * D,
-                    scale * 1.4426950408889634f, 0, ns, 0, G, prefix_len, pf);
+        if (own_lo)
+            O3V_KLAUNCH(attn_decode_mfma_gap_kernel, dim3(ns, Hkv, B), dim3(256), 4 * 32 * 288, stream, (const bf16_t*)Q,
+                        (const bf16_t*)Kc, (const bf16_t*)Vc, part_o, part_ml, k_lo, own_lo, ctx, Hq, Hkv, n_rep, (long)Tmax * D,
+                        (long)Hkv * Tmax * D, scale * 1.4426950408889634f, 0, ns, 0, G, prefix_len, pf);
+        else
+            O3V_KLAUNCH(attn_decode_mfma_kernel, dim3(ns, Hkv, B), dim3(256), 4 * 32 * 288, stream, (const bf16_t*)Q, (const bf16_t*)Kc,
+                        (const bf16_t*)Vc, part_o, part_ml, k_lo, ctx, Hq, Hkv, n_rep, (long)Tmax * D, (long)Hkv * Tmax * D,
+                        scale * 1.4426950408889634f, 0, ns, 0, G, prefix_len, pf);
         O3V_KLAUNCH((attn_decode_combine_kernel<128>), dim3(B * Hq), dim3(128), 0, stream, part_o, part_ml, (bf16_t*)out, ns);
         O3V_CHECK_LAUNCH();
         return O3V_OK;
@@ -857,13 +897,20 @@ extern "C" int o3v_attn_decode_group_prefix(const void* Q, const void* Kc, const
     const int nqb = (G * n_rep + 15) / 16;
     const int n_prefix = nsplit_prefix * Hkv * (B / G), n_own = nsplit_own * Hkv * B;
     dim3 grid(n_prefix + n_own), block(256);
-#define O3V_AG(NQB)                                                                                                         \
-    O3V_KLAUNCH((attn_decode_group_kernel<NQB>), grid, block,                                                                \
+#define O3V_AG2(NQB, GAP)                                                                                                   \
+    O3V_KLAUNCH((attn_decode_group_kernel<NQB, GAP>), grid, block,                                                           \
                 (size_t)((NQB * 16 * 272 + 4 * 32 * 288) > (NQB * 16 * 128 * 4 + 5 * NQB * 16 * 4)                         \
                              ? (NQB * 16 * 272 + 4 * 32 * 288)                                                              \
                              : (NQB * 16 * 128 * 4 + 5 * NQB * 16 * 4)),                                                    \
                 stream, (const bf16_t*)Q, (const bf16_t*)Kc, (const bf16_t*)Vc, part_o, part_ml, k_lo, prefix_len, G, ctx, Hq, \
-                Hkv, n_rep, k_hs, k_bs, sl2, nsplit_prefix, nsplit_own, n_prefix, pf)
+                Hkv, n_rep, k_hs, k_bs, sl2, nsplit_prefix, nsplit_own, n_prefix, pf, own_lo)
+#define O3V_AG(NQB)              \
+    do {                         \
+        if (own_lo)              \
+            O3V_AG2(NQB, true);  \
+        else                     \
+            O3V_AG2(NQB, false); \
+    } while (0)
     if (nqb == 1)
         O3V_AG(1);
     else if (nqb == 2)
@@ -873,6 +920,7 @@ extern "C" int o3v_attn_decode_group_prefix(const void* Q, const void* Kc, const
     else
         O3V_AG(4);
 #undef O3V_AG
+#undef O3V_AG2
     O3V_KLAUNCH((attn_decode_combine_kernel<128>), dim3(B * Hq), dim3(128), 0, stream, part_o, part_ml, (bf16_t*)out,
                 nsplit_tot);
     O3V_CHECK_LAUNCH();

@@ -172,20 +172,26 @@ __device__ __forceinline__ void qkn_finish_head_group(const QkNormRef& qk, const
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
-template <bool FUSED>
+// GAP (shared prefix, suffixes of unequal length left-padded inside the rows' own caches): own_lo_arr[b] slots at the start of
+// row b's own cache are padding, so the logical keys P .. P + own_lo - 1 are masked like the keys below k_lo (they hold finite
+// values: the suffix prefill wrote them).  A wave or a split whose keys all lie in the gap publishes (m, l) = (-1e30, 0), the
+// neutral partial of a split below k_lo.  GAP = false compiles to the code without the test.
+template <bool FUSED, bool GAP = false>
 __device__ __forceinline__ void attn_decode_mfma_body(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ Kc,
                                                       const bf16_t* __restrict__ Vc, float* __restrict__ part_o,
                                                       float* __restrict__ part_ml, const int* __restrict__ k_lo_arr, int ctx,
                                                       int Hq, int Hkv, int n_rep, long k_hs, long k_bs, float scale_log2e,
                                                       int kbeg, int nsplit_tot, int split_off, int G, int P, const int split,
                                                       const int nsplit, const int hk, const int b, char* smem,
-                                                      const AttnHandoff& ho, const PrefixRef pf = PrefixRef{nullptr, nullptr, 0, 0, 1}) {
+                                                      const AttnHandoff& ho, const PrefixRef pf = PrefixRef{nullptr, nullptr, 0, 0, 1},
+                                                      const int* __restrict__ own_lo_arr = nullptr) {
     // keys kbeg..ctx-1 of every row; partials go to slots split_off.. of the row's nsplit_tot (the slots before
     // split_off belong to attn_decode_group_kernel when the rows of a group share their first kbeg keys)
     constexpr int D = 128, KT = 32, VSTRIDE = 288, V_BYTES = KT * VSTRIDE;  // 9216 B per wave; smem: 4 x V slice, reused for the merge
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int fr = lane & 15, fg = lane >> 4;
     const int k_lo = k_lo_arr ? k_lo_arr[b] : 0;
+    const int gap_hi = GAP ? P + own_lo_arr[b] : 0;  // keys P .. gap_hi - 1 are the padding in front of the row's suffix
     char* Vl = smem + wave * V_BYTES;
 
     int chunk = (ctx - kbeg + nsplit - 1) / nsplit;
@@ -317,6 +323,7 @@ __device__ __forceinline__ void attn_decode_mfma_body(const bf16_t* __restrict__
             for (int r = 0; r < 4; ++r) {
                 const int j = key0 + kb * 16 + fg * 4 + r;
                 ok[kb][r] = (j < kw1) && (j >= k_lo);
+                if (GAP) ok[kb][r] = ok[kb][r] && !(j >= P && j < gap_hi);
                 const float sv = ok[kb][r] ? s[kb][r] * scale_log2e : -1e30f;
                 s[kb][r] = sv;
                 mx = fmaxf(mx, sv);

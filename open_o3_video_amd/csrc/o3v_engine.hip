@@ -452,6 +452,7 @@ struct Regime {
     Weights weights, qkv_weights;                     // of the linears; of q/k/v
     bool norm_apart, qkv_fused_norm, qk_norm, group;  // fixed for the call
     bool kv8, kv8_emulate;                            // fp8 K/V cache; its arithmetic emulated on a bf16 cache (tests)
+    const int* own_lo;                                // group rows with left-padded suffixes in their own caches: the gap mask, else NULL
     bool block, layer_block, tail;                    // tried, may fall back: see settle()
 };
 // The one rule of the try-then-fall-back forms: O3V_ERR_SHAPE from the FIRST launch of a form in a call (layer 0 of its first step)
@@ -498,6 +499,9 @@ Regime decide_regime(const o3v_llm_desc* d, const o3v_decode_state* st) {
     r.kv8 = st->k8 != nullptr;
     r.kv8_emulate = !r.kv8 && (st->flags & O3V_DECODE_KV8_EMULATE);
     if (r.kv8 || r.kv8_emulate) r.block = r.layer_block = false;
+    // suffixes behind a shared prefix (o3v_llm_decode_ex has checked that this is a group on a prompt entry): the group kernels mask
+    // each row's padding slots; NULL launches the kernels of before
+    r.own_lo = r.group ? st->own_lo : nullptr;
     return r;
 }
 
@@ -587,10 +591,10 @@ struct Decode {
         }
         if (r.kv8_emulate) TRY(o3v_kv8_roundtrip(kc(l), vc(l), (long)B * Hkv, st->Tmax, slot0 + step, 1, D, s));
         if (r.group)
-            return o3v_attn_decode_group_prefix(w.q, kc(l), vc(l), st->kprefix ? (const char*)st->kprefix + l * pre_stride : nullptr,
-                                                st->kprefix ? (const char*)st->vprefix + l * pre_stride : nullptr, st->prefix_cap,
-                                                st->rows_per_prompt, w.att, st->part_o, st->part_ml, st->k_lo, B, st->group, Hq, Hkv, D,
-                                                st->S, st->S + step + 1, st->Tmax, st->nsplit, scale, s);
+            return o3v_attn_decode_group_prefix_lo(w.q, kc(l), vc(l), st->kprefix ? (const char*)st->kprefix + l * pre_stride : nullptr,
+                                                   st->kprefix ? (const char*)st->vprefix + l * pre_stride : nullptr, st->prefix_cap,
+                                                   st->rows_per_prompt, w.att, st->part_o, st->part_ml, st->k_lo, r.own_lo, B, st->group,
+                                                   Hq, Hkv, D, st->S, st->S + st->own_past + step + 1, st->Tmax, st->nsplit, scale, s);
         return o3v_attn_decode(w.q, kc(l), vc(l), w.att, st->part_o, st->part_ml, st->k_lo, B, Hq, Hkv, D, st->S + step + 1, st->Tmax,
                                st->nsplit, scale, s);
     }
@@ -681,15 +685,17 @@ extern "C" int o3v_llm_decode_ex(const o3v_llm_desc* d, const o3v_decode_state* 
     // shared prompt entries: the caches hold only the generated tokens (slot = step), the prompt K/V live once per prompt
     const bool pfx = st->kprefix != nullptr;
     if (B <= 0 || B > 32 || step0 < 0 || n_steps < 0 || step0 + n_steps > st->Tnew ||
-        (pfx ? st->Tnew : st->S + st->Tnew) > st->Tmax + 1)
+        (pfx ? st->own_past + st->Tnew : st->S + st->Tnew) > st->Tmax + 1)
         return O3V_ERR_ARG;
+    // suffixes behind a shared prefix: a group on a prompt entry, bf16 K/V
+    if ((st->own_past || st->own_lo) && (st->own_past < 0 || !pfx || st->group <= 1 || st->k8)) return O3V_ERR_ARG;
     if (pfx && (!st->vprefix || st->group <= 1 || st->rows_per_prompt <= 0 || (B % st->rows_per_prompt) || st->S > st->prefix_cap))
         return O3V_ERR_ARG;
     if (st->k8 && (!st->v8 || !st->k8s || !st->v8s || st->group > 1 || pfx || st->nsplit <= 0)) return O3V_ERR_ARG;
     if (st->k8 && d->head_dim != 128) return O3V_ERR_SHAPE;
     Decode c{d, st, s, decide_regime(d, st), (long long*)st->host_stats, step0};
     c.B = B, c.H = d->hidden, c.Hq = d->heads, c.Hkv = d->kv_heads, c.D = d->head_dim, c.I = d->inter, c.V = d->vocab;
-    c.QD = c.Hq * c.D, c.NQKV = (c.Hq + 2 * c.Hkv) * c.D, c.slot0 = pfx ? 0 : st->S;  // slot0: cache slot of generated token 0
+    c.QD = c.Hq * c.D, c.NQKV = (c.Hq + 2 * c.Hkv) * c.D, c.slot0 = pfx ? st->own_past : st->S;  // slot0: cache slot of generated token 0
     if (st->ws_bytes < o3v_llm_workspace_bytes(d, B) || !carve_llm(d, B, st->workspace, st->ws_bytes, c.w))
         return O3V_ERR_WORKSPACE;
     c.scale = 1.0f / sqrtf((float)c.D);

@@ -61,7 +61,7 @@ def visual_identity(pixel_values, grid, frames, vis_embeds, pixel_values_videos,
 class DecodePlan(NamedTuple):
     """What one generate call decides about its decode before any buffer exists (plan_decode)."""
     B: int                  # decode rows: B0 prompts x G completions
-    own_splits: int         # 128-key chunks of a row's generated tokens
+    own_splits: int         # 128-key chunks of a row's own keys: its generated tokens (and its suffix behind a shared prefix)
     shared_prompt: bool     # the prompt's K/V is kept once per prompt (kc0 / vc0); the rows' caches hold only generated tokens
     Tmax: int               # slots per row of the decode caches
     nsplit: int             # o3v_decode_state.nsplit: context splits of the decode attention, negative = shared-read group kernel
@@ -71,20 +71,24 @@ class DecodePlan(NamedTuple):
 
 def plan_decode(num_attention_heads: int, num_key_value_heads: int, head_dim: int, B0: int, G: int, S: int, T: int,
                 group_attention: bool = True, group_attention_mode: str = "auto", fused: bool = True, tail_norm: bool = False,
-                nsplit_override: Optional[int] = None) -> DecodePlan:
+                nsplit_override: Optional[int] = None, suffix: int = 0) -> DecodePlan:
     """The decode attention plan of a generate call: B0 prompts of S slots, G completions each, T new tokens.  Pure arithmetic on
     the model's head geometry and the engine's switches (`fused`: the one-launch decode forms are allowed in this call;
-    `nsplit_override`: the O3V_NSPLIT A/B switch)."""
+    `nsplit_override`: the O3V_NSPLIT A/B switch).
+    `suffix` = Lmax > 0 (generate(shared_prefix_len=S)): the G rows are G different continuations of ONE prefix of S tokens; each row's
+    own cache starts with its suffix, left-padded to Lmax slots, and the generated tokens follow.  The group, sub-group and split
+    choice is that of G completions of one prompt; only the rows' own key range grows by Lmax."""
     B = B0 * G
+    suffix = int(suffix)
     # G completions of a prompt share its K/V (head_dim 128, own keys in <= 32 splits): the prompt's K/V is kept ONCE
     # (kc0 / vc0) and every row's cache holds only its generated tokens -- no G-fold copy of the prompt
-    own_splits = (T + 127) // 128
+    own_splits = (suffix + T + 127) // 128
     shared_prompt = G > 1 and head_dim == 128 and own_splits <= 32 and group_attention
-    Tmax = T if shared_prompt else S + T
+    Tmax = suffix + T if shared_prompt else S + suffix + T
     # context splits of the decode attention: one 128-key chunk per block at 1-4 rows; from 8 rows on fewer, longer chunks
     # so that the grid stays near 640 blocks (measured, 7B: 8 rows 40 -> 20 splits 3.85 -> 3.72 ms/step; 16 independent rows
     # 32 -> 8 splits 2020 -> 2128 tok/s; 2 and 4 rows are best at 40)
-    nsplit = max(1, min(64, (S + T + 127) // 128, max(1, 640 // max(1, B * num_key_value_heads))))
+    nsplit = max(1, min(64, (S + suffix + T + 127) // 128, max(1, 640 // max(1, B * num_key_value_heads))))
     if nsplit_override is not None:
         nsplit = nsplit_override
     # G completions of a prompt share its K/V: the group kernel reads the prompt keys once per group (head_dim 128,
@@ -170,18 +174,21 @@ class _DecodeBuffers:
     The structs hold bare addresses, so this object lives until the last o3v_llm_decode_ex call and the final check_waits()."""
 
     def __init__(self, eng: "O3VEngine", plan: DecodePlan, S, T, G, ids_rep, pad_rep, eos_token_ids, row_ids, return_margins, n_lp,
-                 sampling, knobs, cosd, sind, logits, kc, vc, kc0, vc0, kv8=None, kv8_emulate=False):
+                 sampling, knobs, cosd, sind, logits, kc, vc, kc0, vc0, kv8=None, kv8_emulate=False, own=None):
         tc, dev = eng.cfg.text, eng.dev
         B, V = plan.B, tc.vocab_size
         zeros = lambda shape, dtype: torch.zeros(shape, dtype=dtype, device=dev)
         empty = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=dev)
         addr = lambda t: 0 if t is None else t.data_ptr()
         # kv8 = (k8, v8, k8s, v8s): the fp8 K/V caches; kc / vc are then the bf16 staging rows [B, Hkv, 1, D] of the new token
+        # own = (own_past, own_lo i32 [B]): the rows are suffixes behind ONE shared prefix of S tokens (kc0 / vc0, one entry for all
+        # B rows); their own caches already hold own_past slots, the first own_lo[b] of them padding.  ids_rep is then the rows'
+        # own left-padded prompts (any width), pad_rep the padding in front of the prefix
         self.caches, self.tables, self.logits = (kc, vc, kc0, vc0, kv8), (cosd, sind), logits
         self.seen = zeros((B, V), torch.uint8)
         if knobs["rep_penalty"] != 1.0:
             ids_dev = torch.from_numpy(ids_rep.astype(np.int32)).to(dev)
-            _lib.call("o3v_mark_seen", _ptr(ids_dev), _ptr(self.seen), B, S, V, _stream())
+            _lib.call("o3v_mark_seen", _ptr(ids_dev), _ptr(self.seen), B, ids_rep.shape[1], V, _stream())
         self.cur_tok, self.finished = zeros(B, torch.int32), zeros(B, torch.int32)
         self.out_ids = torch.full((B, T), knobs["pad_id"], dtype=torch.int32, device=dev)
         self.margins = zeros((B, T), torch.float32) if return_margins else None
@@ -215,15 +222,19 @@ class _DecodeBuffers:
             if getattr(eng, "_debug_poison_sync", False):     # test hook: tickets that can never reach "last" -> the waits give up
                 self.sync[:1024].view(torch.int32).fill_(0x40000000)
         shared = plan.shared_prompt
-        self.st = _lib.DecodeState(B=B, S=S, Tmax=plan.Tmax, Tnew=T, nsplit=plan.nsplit, x=self.x.data_ptr(), kcache=kc.data_ptr(),
-                                   vcache=vc.data_ptr(), cosT=cosd.data_ptr(), sinT=sind.data_ptr(), logits=logits.data_ptr(),
-                                   seen=self.seen.data_ptr(), cur_tok=self.cur_tok.data_ptr(), finished=self.finished.data_ptr(),
-                                   out_ids=self.out_ids.data_ptr(), margins=addr(self.margins), eos_ids=self.eos.data_ptr(),
-                                   k_lo=self.k_lo.data_ptr(), row_id=self.rid.data_ptr(), part_o=self.part_o.data_ptr(),
-                                   part_ml=self.part_ml.data_ptr(), sample_scratch=self.scratch.data_ptr(),
-                                   workspace=self.ws.data_ptr(), ws_bytes=nbytes, group=plan.group, sync=addr(self.sync),
-                                   kprefix=kc0.data_ptr() if shared else 0, vprefix=vc0.data_ptr() if shared else 0,
-                                   prefix_cap=S if shared else 0, rows_per_prompt=G if shared else 0, **knobs)
+        self.st = _lib.DecodeStateOwn(B=B, S=S, Tmax=plan.Tmax, Tnew=T, nsplit=plan.nsplit, x=self.x.data_ptr(), kcache=kc.data_ptr(),
+                                      vcache=vc.data_ptr(), cosT=cosd.data_ptr(), sinT=sind.data_ptr(), logits=logits.data_ptr(),
+                                      seen=self.seen.data_ptr(), cur_tok=self.cur_tok.data_ptr(), finished=self.finished.data_ptr(),
+                                      out_ids=self.out_ids.data_ptr(), margins=addr(self.margins), eos_ids=self.eos.data_ptr(),
+                                      k_lo=self.k_lo.data_ptr(), row_id=self.rid.data_ptr(), part_o=self.part_o.data_ptr(),
+                                      part_ml=self.part_ml.data_ptr(), sample_scratch=self.scratch.data_ptr(),
+                                      workspace=self.ws.data_ptr(), ws_bytes=nbytes, group=plan.group, sync=addr(self.sync),
+                                      kprefix=kc0.data_ptr() if shared else 0, vprefix=vc0.data_ptr() if shared else 0,
+                                      prefix_cap=int(kc0.shape[3]) if shared else 0, rows_per_prompt=G if shared else 0, **knobs)
+        self.own_lo = None
+        if own is not None:
+            self.own_lo = torch.from_numpy(np.ascontiguousarray(own[1], dtype=np.int32)).to(dev)
+            self.st.own_past, self.st.own_lo = int(own[0]), self.own_lo.data_ptr()
         # decode forwards, launches in their layer loops, fused / stand-alone attention halves
         self.host_stats = (C.c_longlong * 4)(0, 0, 0, 0)
         self.st.host_stats = C.cast(self.host_stats, C.c_void_p)
@@ -528,16 +539,20 @@ class O3VEngine:
                 torch.empty(shape, dtype=torch.bfloat16, device=self.dev))
 
     def prefill(self, x: torch.Tensor, pos3: np.ndarray, pad: Sequence[int], B: int, S: int, kc, vc, past: int = 0,
-                deepstack=None, prefix=None):
+                deepstack=None, prefix=None, own_lo=None):
         """Runs the prompt through the LLM (TF:790-872); x [B*S,H] becomes the last layer's residual stream.
         past > 0: `past` tokens per row are already computed (HF `past_key_values` semantics); x / pos3 are the S tokens
         after them.  By default they sit in slots 0..past-1 of kc / vc.  prefix = (kc0, vc0, rows_per_prefix): they sit ONCE
         per prompt in kc0 / vc0 [layers, B/rows_per_prefix, Hkv, >=past, D] instead, and kc / vc hold only the new tokens (the
         G completions of a prompt behind one copy of its K/V).  deepstack = (input_ids, vis [1+n_deep, n, H]) of a Qwen3-VL
-        prompt: the DeepStack features are added after the first decoder layers at the visual rows (TF3:839-862)."""
+        prompt: the DeepStack features are added after the first decoder layers at the visual rows (TF3:839-862).
+        own_lo [B] (with prefix): the first own_lo[b] of row b's S tokens are left padding (suffixes of unequal length behind one
+        prefix); their keys are masked, their rows of x carry no meaning."""
         Tmax = kc.shape[3]
         cos, sin = self.mrope_table(pos3.reshape(3, B * S))
-        tiles = torch.from_numpy(indexing.prefill_tiles(B, S, pad, past=past)).to(self.dev)
+        if own_lo is not None and prefix is None:
+            raise ValueError("own_lo needs a shared prefix entry")
+        tiles = torch.from_numpy(indexing.prefill_tiles(B, S, pad, past=past, own_lo=own_lo)).to(self.dev)
         nbytes = _lib.load().o3v_llm_workspace_bytes(C.byref(self.w.llm), B * S)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
         opts = _lib.PrefillOpts()
@@ -603,7 +618,8 @@ class O3VEngine:
                  sync_timings: bool = False, prefix_key=None, pixel_values_videos=None, video_grid_thw=None, video_frames=None,
                  second_per_grid_ts=None, logprobs: int = 0, prompt_logprobs: int = 0, min_p: float = 0.0,
                  presence_penalty: float = 0.0, frequency_penalty: float = 0.0, min_new_tokens: int = 0, token_bias=None,
-                 allowed_token_ids=None, banned_token_ids=None, stop_checker=None, _fused_ok: bool = True) -> GenerateOutput:
+                 allowed_token_ids=None, banned_token_ids=None, stop_checker=None, shared_prefix_len: Optional[int] = None,
+                 _fused_ok: bool = True) -> GenerateOutput:
         """HF-semantics generate.  `num_return_sequences=G` shares ONE ViT pass and ONE prefill across the G
         completions of a prompt (the reference recomputes both G times, TF:1493-1579) and fans the KV cache out.
 
@@ -626,7 +642,16 @@ class O3VEngine:
         and buffers are the plain ones.  `stop_checker(ids)` is called at every chunk boundary (`steps_per_sync` steps) with the
         int64 CPU tensor [rows, done] of what has been emitted; it returns {row: n} (or (row, n) pairs): row ends after its first n
         tokens.  Such a row emits pad from the next step on, what it emitted past n is replaced by pad, and the trailing-pad trim
-        counts it as finished at n."""
+        counts it as finished at n.
+
+        `shared_prefix_len=P` ("one video, several questions"; needs num_return_sequences == 1): the rows, given left-padded as
+        usual, agree in their first P real tokens, every visual placeholder lies inside those, and the visual inputs are those of
+        ONE row.  The prefix is prefilled once (looked up and stored under `prefix_key` like a single prompt), the rows' suffixes
+        run behind it as one short prefill, and the rows decode as a group that reads the prefix K/V once per step; each row's own
+        cache holds its suffix, left-padded to the longest, and its generated tokens (indexing.shared_prefix_layout, plan_decode's
+        `suffix`).  A mismatch raises ValueError.  Shapes the group kernels do not serve (head_dim != 128, one row, more than 32
+        own-key splits, prompt_logprobs, group_attention off) run as independent rows on the replicated visual inputs;
+        timings["shared_prefix_rows"] tells which ran (rows in the group, 0 = independent rows)."""
         cfg, tc = self.cfg, self.cfg.text
         ids, mask, pad = prompt_arrays(input_ids, attention_mask)
         B0, S = ids.shape
@@ -648,11 +673,25 @@ class O3VEngine:
         if self.kv_cache_dtype not in ("bf16", "fp8"):
             raise ValueError(f"kv_cache_dtype={self.kv_cache_dtype!r}: 'bf16' or 'fp8'")
 
+        P = Lmax = 0    # shared prefix: its length and the longest suffix behind it; 0 = none, or it runs as independent rows
+        if shared_prefix_len is not None:
+            if G != 1:
+                raise ValueError("shared_prefix_len needs num_return_sequences == 1")
+            P, Lmax = int(shared_prefix_len), int(S - pad.min()) - int(shared_prefix_len)
+
         def make_plan(fused):
+            if P:   # the B0 rows as one group behind one prefix of P tokens
+                return plan_decode(tc.num_attention_heads, tc.num_key_value_heads, tc.head_dim, 1, B0, P, T, self.group_attention,
+                                   self.group_attention_mode, fused, self.tail_norm, int(nsplit_env) if nsplit_env else None,
+                                   suffix=Lmax)
             return plan_decode(tc.num_attention_heads, tc.num_key_value_heads, tc.head_dim, B0, G, S, T, self.group_attention,
                                self.group_attention_mode, fused, self.tail_norm, int(nsplit_env) if nsplit_env else None)
 
         plan = make_plan(self.fused_decode and _fused_ok)
+        replicate = False
+        if P and (n_plp or not plan.shared_prompt):     # shapes the group kernels do not serve: independent rows
+            P, replicate = 0, True
+            plan = make_plan(self.fused_decode and _fused_ok)
         # fp8 K/V (or, test hook, its arithmetic emulated on bf16 caches): the stand-alone attention kernels, so no hand-off buffer
         emulate = bool(getattr(self, "_debug_kv8_emulate", False)) and kv_cache_in_effect("fp8", tc.head_dim, plan) == "fp8"
         kv_dtype = "bf16" if emulate else kv_cache_in_effect(self.kv_cache_dtype, tc.head_dim, plan)
@@ -672,32 +711,50 @@ class O3VEngine:
         vis, grid, vgrid, n_img_rows = self._visual(pixel_values, image_grid_thw, frames, vis_embeds, pixel_values_videos, video_grid_thw,
                                                     video_frames)
         mark(1)
-        # ---- positions + prefill (once per prompt); a call asking for prompt log-probs neither reuses nor stores prefix K/V
-        pos, deltas = self._positions(ids, mask, grid, vgrid, second_per_grid_ts)
-        x, kc, vc, kc0, vc0, past, kv8 = self._prefill_prompt(ids, pad, pos, vis, n_img_rows, G, plan, None if n_plp else prefix_key,
-                                                              kv_dtype == "fp8", emulate)
-        tm["prefix_tokens_reused"] = past
+        lay = None
+        if shared_prefix_len is not None:   # the rows' layout behind the prefix; checks them whichever way they run
+            lay = indexing.shared_prefix_layout(ids, mask, int(shared_prefix_len), T, cfg.image_token_id, cfg.video_token_id, pad_id,
+                                                **self._rope_kw(grid, vgrid, second_per_grid_ts))
+            tm["shared_prefix_rows"] = B0 if P else 0
+        if replicate:   # independent rows: every row gets the one row's visual tokens
+            vis, grid, vgrid, n_img_rows, second_per_grid_ts = self._replicate_visual(vis, grid, vgrid, n_img_rows, second_per_grid_ts, B0)
+        kv8, plp = None, None
         self._last_prompt = None
-        if self.reuse_prompt_kv and plan.shared_prompt and B0 == 1:
-            key = self._prompt_key(ids, mask, pos, visual_identity(pixel_values, grid, frames, vis_embeds, pixel_values_videos, vgrid,
-                                                                   video_frames))
-            self._last_prompt = {"key": key, "kc0": kc0, "vc0": vc0, "x_last": x.view(B0, S - past, -1)[0, -1:, :].clone(),
-                                 "deltas": np.array(deltas, copy=True)}
-        plp = self._prompt_logprobs(x.view(B0, S, -1), ids, n_plp) if n_plp else None
-        last = x.view(B0, S - past, -1)[:, -1, :]               # left padding: every row ends at S-1
-        logits0 = self.head(last)                               # [B0, V]
-        logits = logits0.repeat_interleave(G, dim=0).contiguous() if G > 1 else logits0
-        mark(2)
+        if P:
+            # ---- the prefix once, the suffixes behind it; every row's last suffix token gives its first logits
+            x, kc, vc, kc0, vc0, past = self._prefill_shared_prefix(lay, vis, n_img_rows, plan, prefix_key)
+            tm["prefix_tokens_reused"] = past
+            logits = self.head(x.view(B0, Lmax, -1)[:, -1, :])      # [B0, V]
+            mark(2)
+            dpos, ids_rep = lay.decode_pos, ids
+            state = dict(S=P, G=B0, pad_rep=np.zeros(B0, dtype=np.int64), own=(Lmax, lay.own_lo))
+        else:
+            # ---- positions + prefill (once per prompt); a call asking for prompt log-probs neither reuses nor stores prefix K/V
+            pos, deltas = self._positions(ids, mask, grid, vgrid, second_per_grid_ts)
+            x, kc, vc, kc0, vc0, past, kv8 = self._prefill_prompt(ids, pad, pos, vis, n_img_rows, G, plan, None if n_plp else prefix_key,
+                                                                  kv_dtype == "fp8", emulate)
+            tm["prefix_tokens_reused"] = past
+            if self.reuse_prompt_kv and plan.shared_prompt and B0 == 1:
+                key = self._prompt_key(ids, mask, pos, visual_identity(pixel_values, grid, frames, vis_embeds, pixel_values_videos, vgrid,
+                                                                       video_frames))
+                self._last_prompt = {"key": key, "kc0": kc0, "vc0": vc0, "x_last": x.view(B0, S - past, -1)[0, -1:, :].clone(),
+                                     "deltas": np.array(deltas, copy=True)}
+            plp = self._prompt_logprobs(x.view(B0, S, -1), ids, n_plp) if n_plp else None
+            last = x.view(B0, S - past, -1)[:, -1, :]               # left padding: every row ends at S-1
+            logits0 = self.head(last)                               # [B0, V]
+            logits = logits0.repeat_interleave(G, dim=0).contiguous() if G > 1 else logits0
+            mark(2)
+            dpos = indexing.decode_positions(mask, deltas, T)       # [3,B0,T]
+            if G > 1:
+                dpos = np.repeat(dpos, G, axis=1)
+            ids_rep = np.repeat(ids, G, axis=0) if G > 1 else ids
+            state = dict(S=S, G=G, pad_rep=np.repeat(pad, G) if G > 1 else pad, own=None)
         # ---- decode state
-        dpos = indexing.decode_positions(mask, deltas, T)       # [3,B0,T]
-        if G > 1:
-            dpos = np.repeat(dpos, G, axis=1)
         cosd, sind = self.mrope_table(dpos.reshape(3, B * T))
-        ids_rep = np.repeat(ids, G, axis=0) if G > 1 else ids
         knobs = dict(pad_id=pad_id, n_eos=len(eos_token_ids), do_sample=int(do_sample), rep_penalty=float(repetition_penalty),
                      temperature=float(temperature), top_p=float(top_p), seed=int(seed) & (2 ** 64 - 1), top_k=max(0, int(top_k or 0)))
-        buf = _DecodeBuffers(self, plan, S, T, G, ids_rep, np.repeat(pad, G) if G > 1 else pad, eos_token_ids, row_ids, return_margins,
-                             n_lp, sampling, knobs, cosd, sind, logits, kc, vc, kc0, vc0, kv8, emulate)
+        buf = _DecodeBuffers(self, plan, state["S"], T, state["G"], ids_rep, state["pad_rep"], eos_token_ids, row_ids, return_margins,
+                             n_lp, sampling, knobs, cosd, sind, logits, kc, vc, kc0, vc0, kv8, emulate, own=state["own"])
         tm["kv_cache_dtype"] = kv_dtype
         tm["kv_cache_bytes"] = int((kc.numel() + vc.numel() + (kc0.numel() + vc0.numel() if plan.shared_prompt else 0)) * 2 +
                                    sum(t.numel() * t.element_size() for t in kv8 or ()))
@@ -711,7 +768,7 @@ class O3VEngine:
         tm["fused_attention_layers"], tm["standalone_attention_layers"] = int(stats[2]), int(stats[3])
         buf.check_waits()
         if getattr(self, "_debug_keep", False):     # probe hook: the decode's state after the last step
-            self._debug_last = {"kc": kc, "vc": vc, "logits": logits, "x": buf.x, "S": S, "cos": cosd, "sin": sind, "k_lo": buf.k_lo,
+            self._debug_last = {"kc": kc, "vc": vc, "logits": logits, "x": buf.x, "S": state["S"], "cos": cosd, "sin": sind, "k_lo": buf.k_lo,
                                 "nsplit": plan.nsplit, "Tmax": plan.Tmax, "out_ids": buf.out_ids,
                                 **dict(zip(("k8", "v8", "k8s", "v8s"), kv8 or (None,) * 4))}
         gen = buf.out_ids[:, :done].to(torch.int64)
@@ -729,6 +786,58 @@ class O3VEngine:
             lp = Logprobs(lp.token[:, :done], lp.rank[:, :done], lp.top_ids[:, :done], lp.top[:, :done])
         return GenerateOutput(sequences=seqs, margins=None if margins is None else margins[:, :done], n_steps=done,
                               timings=tm, logprobs=lp, prompt_logprobs=plp)
+
+    def _rope_kw(self, grid, vgrid, second_per_grid_ts):
+        """indexing.rope_index's keywords for this model (as _positions passes them)."""
+        cfg = self.cfg
+        return dict(image_grid_thw=grid, merge=cfg.vision.spatial_merge_size, video_grid_thw=vgrid,
+                    second_per_grid_ts=second_per_grid_ts, tokens_per_second=cfg.vision.tokens_per_second,
+                    split_video_frames=self.q3, mode="tf5" if self.q3 else self.position_mode)
+
+    @staticmethod
+    def _replicate_visual(vis, grid, vgrid, n_img_rows, second_per_grid_ts, B):
+        """One row's visual tokens for B rows that all hold its placeholders: [image tokens ; video tokens] -> [B x image ; B x video]
+        (the order embed_source_rows consumes), grids and seconds-per-grid repeated alike."""
+        if vis is None:
+            return vis, grid, vgrid, n_img_rows, second_per_grid_ts
+        n_img = vis.shape[-2] if n_img_rows is None else int(n_img_rows)
+        vis = torch.cat([vis[..., :n_img, :]] * B + [vis[..., n_img:, :]] * B, dim=-2)
+        tile = lambda g: None if g is None else np.tile(np.asarray(g).reshape(-1, 3), (B, 1))
+        spg = second_per_grid_ts
+        if spg is not None:
+            spg = np.tile(np.asarray(spg.cpu() if torch.is_tensor(spg) else spg, dtype=np.float64).reshape(-1), B)
+        return vis, tile(grid), tile(vgrid), None if n_img_rows is None else n_img * B, spg
+
+    def _prefill_shared_prefix(self, lay, vis, n_img_rows, plan: DecodePlan, prefix_key):
+        """The prompt stage of generate(shared_prefix_len=P): the prefix as ONE un-padded row through the route of _prefill_prompt
+        (looked up and stored under `prefix_key`; Qwen3-VL DeepStack rows all lie in it), then the B suffixes, left-padded to Lmax,
+        behind it into the rows' own caches.
+        -> (x: last-layer rows of the suffixes [B * Lmax, H], kc, vc [layers, B, Hkv, plan.Tmax, D], kc0, vc0: the prefix entry,
+        past: prefix tokens reused).  A stored entry that covers the whole prefix is used where it lies: nothing here writes it."""
+        pids = lay.prefix_ids
+        P = pids.shape[1]
+        B, Lmax = lay.suffix_ids.shape
+        past, ent = 0, self._prefix.get(prefix_key) if prefix_key is not None else None
+        if ent is not None:
+            n = min(len(ent["ids"]), P)
+            neq = np.flatnonzero(ent["ids"][:n] != pids[0, :n])
+            past = int(neq[0]) if neq.size else int(n)
+        if past == P:
+            kc0, vc0 = ent["k"], ent["v"]
+        else:
+            kc0, vc0 = self.alloc_cache(1, P)
+            if past:
+                kc0[:, :, :, :past].copy_(ent["k"][:, :, :, :past])
+                vc0[:, :, :, :past].copy_(ent["v"][:, :, :, :past])
+            x0 = self.embed(pids, vis, first=past, n_image_rows=n_img_rows)
+            self.prefill(x0, lay.prefix_pos[:, :, past:], [0], 1, P - past, kc0, vc0, past=past,
+                         deepstack=(pids, vis) if self.q3 else None)
+            if prefix_key is not None:
+                self._prefix_store(prefix_key, pids[0], kc0, vc0)
+        kc, vc = self.alloc_cache(B, plan.Tmax)
+        x = self.embed(lay.suffix_ids, None)
+        self.prefill(x, lay.suffix_pos, np.zeros(B, dtype=np.int64), B, Lmax, kc, vc, past=P, prefix=(kc0, vc0, B), own_lo=lay.own_lo)
+        return x, kc, vc, kc0, vc0, past
 
     def _prefill_prompt(self, ids, pad, pos, vis, n_img_rows, G, plan: DecodePlan, prefix_key, kv8: bool = False,
                         kv8_emulate: bool = False):

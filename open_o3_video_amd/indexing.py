@@ -8,6 +8,7 @@ the attention kernel consumes.  Parity with the oracle / HF goldens: tests/test_
 from __future__ import annotations
 
 from functools import lru_cache
+from typing import NamedTuple
 
 import numpy as np
 
@@ -66,16 +67,22 @@ def segment_tiles(cu):
     return np.asarray(out, dtype=np.int32).reshape(-1, 8)
 
 
-def prefill_tiles(B, S, pad, tile=PREFILL_TILE, past=0):
+def prefill_tiles(B, S, pad, tile=PREFILL_TILE, past=0, own_lo=None):
     """Causal tiles over B left-padded rows of S new tokens whose K/V sit in the cache at slots past..past+S-1
     (slots 0..past-1 hold an already-computed prompt prefix; `pad` counts the left padding inside that prefix
-    when past > 0, inside the new tokens otherwise)."""
+    when past > 0, inside the new tokens otherwise).  own_lo (past > 0, shared prompt entry): the first own_lo[b] of row b's
+    S new tokens are left padding of their own -- descriptor word 7, the keys past .. past + own_lo[b] - 1 are masked."""
+    if own_lo is not None and not past and any(int(v) for v in own_lo):
+        raise ValueError("own_lo needs a prefix in front of the new tokens (past > 0)")
     out = []
     for b in range(B):
         pb = int(pad[b])
+        lo = 0 if own_lo is None else int(own_lo[b])
+        if not 0 <= lo < S:
+            raise ValueError(f"own_lo[{b}] = {lo} outside [0, {S})")
         first = 0 if past else (pb // tile) * tile
         for q0 in range(first, S, tile):
-            out.append((b * S + q0, min(tile, S - q0), 0, past + S, past + q0, pb, b, 0))
+            out.append((b * S + q0, min(tile, S - q0), 0, past + S, past + q0, pb, b, lo))
     # longest first: a causal tile's work grows with its row offset and workgroups are dispatched in list order, so the heavy
     # tiles start first and the light ones fill the tail (measured: prefill S = 4490 62.5 -> 62.2 ms, S = 20k 398 -> 396 ms:
     # within noise -- two rounds of 28 heads x 36 tiles already mix all sizes -- kept because it cannot hurt)
@@ -176,6 +183,63 @@ def decode_positions(attention_mask, deltas, n_new):
     t = np.arange(n_new, dtype=np.int64)[None, :]
     p = n_real[:, None] + t + np.asarray(deltas).reshape(-1, 1)
     return np.broadcast_to(p[None], (3,) + p.shape).copy()  # [3,B,n_new]
+
+
+class SharedPrefixLayout(NamedTuple):
+    """What shared_prefix_layout returns: B rows = one shared prefix of P tokens + a suffix each, left-padded to Lmax."""
+    prefix_ids: np.ndarray    # i64 [1, P]
+    suffix_ids: np.ndarray    # i64 [B, Lmax], row b's suffix in columns own_lo[b].., `pad_token` in front of it
+    own_lo: np.ndarray        # i32 [B] = Lmax - len(suffix b): the padding slots at the start of row b's own cache
+    prefix_pos: np.ndarray    # i64 [3, 1, P]
+    suffix_pos: np.ndarray    # i64 [3, B, Lmax], 0 in the padding slots
+    decode_pos: np.ndarray    # i64 [3, B, n_new]
+    deltas: np.ndarray        # i64 [B]
+
+
+def shared_prefix_layout(input_ids, attention_mask, P, n_new, image_token_id, video_token_id=None, pad_token=0, **rope_kw):
+    """B left-padded rows that agree in their first P real tokens ("one video, several questions") -> SharedPrefixLayout.
+
+    The prefix is taken un-padded (a batch of one without left padding, whatever padding the rows carry); every row keeps at least
+    one token behind it, whose hidden state gives the row's first logits.  Every position is rope_index / decode_positions of the
+    un-padded row taken alone; `rope_kw` goes to rope_index and describes the visual blocks of ONE row (image_grid_thw,
+    video_grid_thw, merge, second_per_grid_ts, tokens_per_second, split_video_frames, mode).
+    Raises ValueError when P < 1, a row has no token behind P, the rows differ inside P, or a visual placeholder sits behind P."""
+    ids = np.asarray(input_ids, dtype=np.int64)
+    if ids.ndim == 1:
+        ids = ids[None]
+    mask = np.ones_like(ids) if attention_mask is None else np.asarray(attention_mask, dtype=np.int64).reshape(ids.shape)
+    P, n_new = int(P), int(n_new)
+    if P < 1:
+        raise ValueError(f"shared_prefix_len must be at least 1, got {P}")
+    rows = [ids[b][mask[b] != 0] for b in range(ids.shape[0])]
+    B = len(rows)
+    visual = [image_token_id] + ([] if video_token_id is None else [video_token_id])
+    for b, row in enumerate(rows):
+        if row.shape[0] <= P:
+            raise ValueError(f"row {b} has {row.shape[0]} tokens: nothing behind a shared prefix of {P}")
+        if not np.array_equal(row[:P], rows[0][:P]):
+            raise ValueError(f"row {b} differs from row 0 inside the shared prefix of {P} tokens")
+        if np.isin(row[P:], visual).any():
+            raise ValueError(f"row {b} has a visual placeholder behind the shared prefix of {P} tokens")
+    lens = np.asarray([row.shape[0] - P for row in rows], dtype=np.int64)
+    Lmax = int(lens.max())
+    own_lo = (Lmax - lens).astype(np.int32)
+    suffix_ids = np.full((B, Lmax), int(pad_token), dtype=np.int64)
+    suffix_pos = np.zeros((3, B, Lmax), dtype=np.int64)
+    deltas = np.zeros(B, dtype=np.int64)
+    prefix_pos = None
+    for b, row in enumerate(rows):
+        pos, dl = rope_index(row[None], None, rope_kw.get("image_grid_thw"), image_token_id, video_token_id=video_token_id,
+                             **{k: v for k, v in rope_kw.items() if k != "image_grid_thw"})
+        if prefix_pos is None:
+            prefix_pos = pos[:, :, :P].copy()
+        elif not np.array_equal(pos[:, :, :P], prefix_pos):     # same ids, same grids: cannot differ
+            raise ValueError(f"row {b}: positions inside the shared prefix differ from row 0's")
+        suffix_ids[b, own_lo[b]:] = row[P:]
+        suffix_pos[:, b, own_lo[b]:] = pos[:, 0, P:]
+        deltas[b] = dl[0]
+    dpos = decode_positions(np.asarray([[1] * int(P + n) + [0] * int(Lmax - n) for n in lens]), deltas, n_new)
+    return SharedPrefixLayout(rows[0][None, :P].copy(), suffix_ids, own_lo, prefix_pos, suffix_pos, dpos, deltas)
 
 
 def embed_source_rows(input_ids, image_token_id, video_token_id=None, n_image_rows=None):

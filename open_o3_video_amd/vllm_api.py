@@ -197,6 +197,33 @@ def _load_tokenizer(path):
     return AutoTokenizer.from_pretrained(path, local_files_only=True)
 
 
+def shared_prefix_groups(ids_list, vkeys, visual_ids):
+    """Which requests of one generate() call run as shared-prefix groups: -> (groups: [(P, positions)], rest: positions that go
+    the ordinary way), both in input order.  Requests with the same visual key form a group when there are at least two of them
+    and their longest common token prefix, capped so that every request keeps a token behind it, ends at or after the last visual
+    placeholder (P >= 1: everything visual, and whatever text precedes it, is shared)."""
+    by_key = {}
+    for i, k in enumerate(vkeys):
+        by_key.setdefault(k, []).append(i)
+    groups, rest = [], []
+    for k, at in by_key.items():
+        P = 0
+        if len(at) >= 2:
+            first = ids_list[at[0]]
+            P = min(len(ids_list[i]) for i in at) - 1
+            for i in at[1:]:
+                row = ids_list[i]
+                P = next((j for j in range(P) if row[j] != first[j]), P)
+            last_visual = max((j for j, t in enumerate(first) if t in visual_ids), default=-1)
+            if P <= last_visual or any(t in visual_ids for i in at for t in ids_list[i][P:]):
+                P = 0
+        if P >= 1:
+            groups.append((P, at))
+        else:
+            rest += at
+    return groups, sorted(rest)
+
+
 class LLM:
     IMAGE_PAD = "<|image_pad|>"
     VIDEO_PAD = "<|video_pad|>"
@@ -207,7 +234,8 @@ class LLM:
                  max_num_seqs: int = 8, engine: Optional[O3VEngine] = None, tokenizer: Any = None,
                  min_pixels: int = 56 * 56, max_pixels: int = 14 * 14 * 4 * 1280, device="cuda",
                  enable_prefix_caching: bool = True, quantization: Optional[str] = None, mm_processor_kwargs: Optional[dict] = None,
-                 position_mode: str = "pinned", fp8_prefill: bool = False, kv_cache_dtype: str = "auto", **_):
+                 position_mode: str = "pinned", fp8_prefill: bool = False, kv_cache_dtype: str = "auto",
+                 share_video_prefix: bool = False, **_):
         # vLLM's keyword: "fp8" / "fp8_e4m3" keep the K/V cache of independent-row decodes as e4m3fn rows with one power-of-two scale
         # per (token, kv head) (O3VEngine.kv_cache_dtype; not vLLM's per-tensor k_scale / v_scale: parity unpinned against vLLM)
         kv_dtypes = {"auto": "bf16", "bfloat16": "bf16", "fp8": "fp8", "fp8_e4m3": "fp8"}
@@ -268,6 +296,11 @@ class LLM:
         # prompts over identical frames are prefilled; vLLM's `enable_prefix_caching` keyword switches it
         self.enable_prefix_caching = bool(enable_prefix_caching)
         self.prefix_tokens_reused = 0
+        # opt-in: the requests of one generate() call over the same visual content ("five questions about one video") run as ONE
+        # engine call that prefills their common prefix once and decodes them as a group reading its K/V once per step
+        # (O3VEngine.generate(shared_prefix_len=...)); counted in shared_prefix_calls / shared_prefix_rows
+        self.share_video_prefix = bool(share_video_prefix)
+        self.shared_prefix_calls = self.shared_prefix_rows = 0
         # native video inputs: HF's Qwen2_5_VLProcessor gives every video second_per_grid_ts = temporal_patch_size / fps with
         # fps = 2.0 unless mm_processor_kwargs={"fps": ...} says otherwise (TF:models/qwen2_5_vl/processing_qwen2_5_vl.py:143-153;
         # the reference passes none, R:eval/models/model_vllm.py:18-26)
@@ -627,32 +660,54 @@ class LLM:
             # several requests in one call (vLLM batches them, R:eval/models/model_vllm.py:23 max_num_seqs): decode up to
             # max_num_seqs of them together, left padded, every streamed weight byte shared by the rows of the step
             rows_per_call = min(self.max_num_seqs, O3VEngine.MAX_ROWS)
-            for c0 in range(0, len(prepared), rows_per_call):
-                chunk = prepared[c0:c0 + rows_per_call]
+            results = [None] * len(prepared)
+
+            def run_rows(at, shared=None):
+                """One engine call over the requests prepared[i], i in `at`.  shared = (P, vkey): they share their first P tokens and
+                the visual content `vkey` -- one row's visual inputs, the prefix prefilled once, the rows decoded as a group."""
+                chunk = [prepared[i] for i in at]
                 L = max(len(p[1]) for p in chunk)
                 pad = self.cfg.pad_token_id
                 rows = [[pad] * (L - len(p[1])) + p[1] for p in chunk]
                 mask = [[0] * (L - len(p[1])) + [1] * len(p[1]) for p in chunk]
-                grid_parts = [p[3] for p in chunk if p[3] is not None]
-                vgrid_parts = [p[6] for p in chunk if p[6] is not None]
-                spg_all = [x for p in chunk if p[7] for x in p[7]]
+                vis_of = chunk[:1] if shared else chunk
+                grid_parts = [p[3] for p in vis_of if p[3] is not None]
+                vgrid_parts = [p[6] for p in vis_of if p[6] is not None]
+                spg_all = [x for p in vis_of if p[7] for x in p[7]]
                 if stop_strs:
                     common["stop_checker"] = make_checker(len(chunk))[0]
-                out = self.engine.generate(rows, mask, vis_embeds=cat_visual([p[2] for p in chunk], [v for p in chunk for v in p[5]]),
+                extra = {}
+                if shared:
+                    extra = dict(shared_prefix_len=shared[0], prefix_key=shared[1] if self.enable_prefix_caching else None)
+                out = self.engine.generate(rows, mask, vis_embeds=cat_visual([p[2] for p in vis_of], [v for p in vis_of for v in p[5]]),
                                            image_grid_thw=np.concatenate(grid_parts) if grid_parts else None,
                                            video_grid_thw=np.concatenate(vgrid_parts) if vgrid_parts else None,
                                            second_per_grid_ts=spg_all or None,
-                                           row_ids=[base + positions[c0 + i] for i in range(len(chunk))],
+                                           row_ids=[base + positions[i] for i in at],
                                            seed=0 if sp.seed is None else sp.seed,
-                                           prompt_logprobs=0 if n_plp is None else max(1, n_plp), **common)
+                                           prompt_logprobs=0 if n_plp is None else max(1, n_plp), **extra, **common)
+                if shared:
+                    self.shared_prefix_calls += 1
+                    self.shared_prefix_rows += int(out.timings.get("shared_prefix_rows", 0))
+                    self.prefix_tokens_reused += int(out.timings.get("prefix_tokens_reused", 0))
                 lp, plp = _host_logprobs(out.logprobs), _host_logprobs(out.prompt_logprobs)
-                for i, p in enumerate(chunk):
-                    ro = RequestOutput(request_id=str(base + positions[c0 + i]), prompt=p[0], prompt_token_ids=p[1])
+                for i, (at_i, p) in enumerate(zip(at, chunk)):
+                    ro = RequestOutput(request_id=str(base + positions[at_i]), prompt=p[0], prompt_token_ids=p[1])
                     finish(ro, 0, out.sequences[i], L, lp, i)
                     if plp is not None:     # left padding: the row's first real token sits at column L - len(ids)
                         ro.prompt_logprobs = prompt_dicts(plp, i, p[1], L - len(p[1]))
-                    results.append(ro)
+                    results[at_i] = ro
                     self._req += 1
+
+            rest = list(range(len(prepared)))
+            if self.share_video_prefix and n_plp is None:
+                visual_ids = (self.cfg.image_token_id, self.cfg.video_token_id)
+                groups, rest = shared_prefix_groups([p[1] for p in prepared], [p[4] for p in prepared], visual_ids)
+                for P, at in groups:
+                    for c0 in range(0, len(at), rows_per_call):
+                        run_rows(at[c0:c0 + rows_per_call], shared=(P, prepared[at[0]][4]))
+            for c0 in range(0, len(rest), rows_per_call):
+                run_rows(rest[c0:c0 + rows_per_call])
             return results
         for pos, (prompt, ids, vis_i, grid, vkey, vis_v, vgrid, spg) in zip(positions, prepared):
             vis = cat_visual([vis_i], vis_v)
