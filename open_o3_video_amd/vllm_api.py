@@ -403,6 +403,8 @@ class LLM:
         import ctypes as C
         from . import _lib
         fr = fr.to(self.engine.dev).contiguous()
+        if fr.data_ptr() % 8:       # frames that came in on the device as a view into a larger buffer: the kernel reads 8-byte words
+            fr = fr.clone()
         h = torch.zeros(2, dtype=torch.int64, device=fr.device)
         _lib.call("o3v_content_hash128", C.c_void_p(fr.data_ptr()), fr.numel() * fr.element_size(), C.c_void_p(h.data_ptr()),
                   C.c_void_p(torch.cuda.current_stream().cuda_stream))
@@ -625,9 +627,14 @@ class LLM:
             ids = self._tokenize(prompt, 0 if frames is None else frames.shape[0], tpf, placeholders)
             if len(ids) + sp.max_tokens > self.max_model_len:
                 raise ValueError(f"prompt ({len(ids)}) + max_tokens ({sp.max_tokens}) exceeds max_model_len {self.max_model_len}")
-            vkey = tuple(keys) if keys else ("text-only",)      # identifies the visual content of the prompt (prefix-K/V reuse)
             vgrid = np.concatenate(vgrids) if vgrids else None
             spg = [tps / fps] * len(vgrids) if vgrids else None
+            # identifies what the prompt's K/V depend on besides the token ids (prefix-K/V reuse, shared-prefix groups): the visual
+            # content and, with a video, the M-RoPE arithmetic its K rows were rotated with (indexing.rope_index: the modes agree on
+            # images) -- the engine's store is shared by every facade over it
+            vkey = tuple(keys) if keys else ("text-only",)
+            if spg:
+                vkey += (("positions", self.position_mode, tuple(spg)),)
             prepared.append((prompt, ids, vis_i, grid, vkey, vis_v, vgrid, spg))
 
         def cat_visual(img_parts, vid_parts):
