@@ -48,6 +48,20 @@ __device__ __forceinline__ float combine_dim(const float* part_o, size_t bh, int
     return acc;
 }
 
+// The one-launch block spreads the merge of a kv head's n_out = n_rep x D outputs over the head's nsplit workgroups: workgroup
+// `split` merges [*begin, *begin + *count).  Slices are whole groups of 8 elements (16 bytes of bf16 output, two 16-byte loads of
+// fp32 partials per split), ceil(groups / nsplit) groups each, in ascending order; trailing workgroups get an empty slice at
+// n_out.  n_out % 8 == 0.  (C ABI: o3v_attn_merge_slice, o3v_fused.hip.)
+__host__ __device__ inline void attn_merge_slice(int n_out, int nsplit, int split, int* begin, int* count) {
+    const int groups = n_out >> 3, per = (groups + nsplit - 1) / nsplit;
+    const int g0 = split * per < groups ? split * per : groups;
+    const int g1 = g0 + per < groups ? g0 + per : groups;
+    *begin = g0 * 8;
+    *count = (g1 - g0) * 8;
+}
+// LDS of the merge at the largest slice: [nsplit][count] fp32 partials, count * nsplit <= 8 (groups + nsplit - 1), in front of sw
+static_assert(8 * (NREP_MAX * 16 + 63) * 4 <= 33536, "the slice's partials must fit in front of the split weights");
+
 // ------------------------------------------------------------------------------------------------
 // Decode attention on the matrix cores (head_dim 128).  Same swapped-QK^T scheme as attn_tiles_kernel with the
 // n_rep query heads of a kv head as the 16 "query rows" (GQA: K/V bytes are read once for the whole group):
@@ -74,7 +88,7 @@ struct AttnHandoff {
     uint32_t* tmo;        // sticky time-out word
     bf16_t* att_out;      // [B, Hq, D] attention output (input of o_proj)
 #ifdef O3V_STAMPS
-    unsigned long long* stamp;  // diagnostic build (tools/probes/probe_fused.py): this workgroup's {start, wait over, partials out, end, all partials known, slice stored}
+    unsigned long long* stamp;  // diagnostic build (tools/probes/probe_fused.py): this workgroup's {start, wait over, partials out, end, all partials known, slice stored, partials computed (stores issued, not drained)}
     bool no_prefetch;           // ablation: request the first K/V tile only after the wait
 #endif
 };
@@ -373,28 +387,40 @@ __device__ __forceinline__ void attn_decode_mfma_body(const bf16_t* __restrict__
         sl[wave * 16 + fr] = l_tot;
     }
     __syncthreads();
-    for (int i = threadIdx.x; i < n_rep * D; i += 256) {
-        const int q = i / D, d = i % D;
+    // a thread merges 4 consecutive d of one query head (n_rep * D / 4 <= 256 threads) and stores them as ONE 16-byte store, (m, l)
+    // of a head as one 8-byte store: write-through (sc1) when FUSED.  Per element the sum over w is the same chain as ever.
+    const size_t bh0 = (size_t)b * Hq + (size_t)hk * n_rep;  // first (b, head) row of this kv head
+    __amdgpu_buffer_rsrc_t pors, pmrs;
+    if (FUSED) {
+        pors = __builtin_amdgcn_make_buffer_rsrc((void*)(part_o + bh0 * nsplit_tot * D), 0, n_rep * nsplit_tot * D * 4, 0x00020000);
+        pmrs = __builtin_amdgcn_make_buffer_rsrc((void*)(part_ml + bh0 * nsplit_tot * 2), 0, n_rep * nsplit_tot * 2 * 4, 0x00020000);
+    }
+    for (int i = threadIdx.x; i < n_rep * (D / 4); i += 256) {
+        const int q = i / (D / 4), d = (i % (D / 4)) * 4;
         const float mn = fmaxf(fmaxf(sm[q], sm[16 + q]), fmaxf(sm[32 + q], sm[48 + q]));
-        float acc = 0.f, lt = 0.f;
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+        float lt = 0.f;
 #pragma unroll
         for (int w = 0; w < 4; ++w) {
             const float sc = __builtin_amdgcn_exp2f(sm[w * 16 + q] - mn);
-            acc += so[(size_t)(w * 16 + q) * D + d] * sc;
+            acc += *reinterpret_cast<const f32x4*>(so + (size_t)(w * 16 + q) * D + d) * sc;
             lt += sl[w * 16 + q] * sc;
         }
-        const size_t idx = (((size_t)b * Hq + hk * n_rep + q) * nsplit_tot + split_off + split);
-        stf<FUSED>(part_o + idx * D + d, acc);
-        if (d == 0) {
-            stf<FUSED>(part_ml + idx * 2, mn);
-            stf<FUSED>(part_ml + idx * 2 + 1, lt);
+        const int idx = q * nsplit_tot + split_off + split;  // slot of (head q of the group, this split)
+        if (FUSED) {
+            store16_sc1(pors, (uint32_t)(idx * D + d) * 4, __builtin_bit_cast(u32x4, acc));
+            if (d == 0) store8_sc1(pmrs, (uint32_t)idx * 8, (u32x2){__builtin_bit_cast(uint32_t, mn), __builtin_bit_cast(uint32_t, lt)});
+        } else {
+            *reinterpret_cast<f32x4*>(part_o + (bh0 * nsplit_tot + idx) * D + d) = acc;
+            if (d == 0) *reinterpret_cast<float2*>(part_ml + (bh0 * nsplit_tot + idx) * 2) = make_float2(mn, lt);
         }
     }
+    O3V_STAMP(ho.stamp, 6);
     if (!FUSED) return;
 
     // ---- merge of the context splits, spread over the kv head's nsplit workgroups.  One CU moves ~25 GB/s, so a single
-    // workgroup reading all n_rep x nsplit x D partials (143 KB at 7B / 4.6k keys) needs 5+ us; a slice of
-    // ceil(n_rep*D / nsplit) output elements per workgroup needs one round trip.  Ticket 1: the last split tells every
+    // workgroup reading all n_rep x nsplit x D partials (143 KB at 7B / 4.6k keys) needs 5+ us; a slice of the outputs per
+    // workgroup (attn_merge_slice; here nsplit_tot == nsplit) needs one round trip.  Ticket 1: the last split tells every
     // workgroup of the head (mailbox word 1) that all partials are in memory.
     float* sw = reinterpret_cast<float*>(smem + 33536);           // [NREP_MAX][64], behind so / sm / sl
     float* sinv = sw + NREP_MAX * 64;                             // [NREP_MAX]
@@ -412,35 +438,40 @@ __device__ __forceinline__ void attn_decode_mfma_body(const bf16_t* __restrict__
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     __syncthreads();
     O3V_STAMP(ho.stamp, 4);
-    const size_t bh0 = (size_t)b * Hq + (size_t)hk * n_rep;
-    const int n_out = n_rep * D, per = (n_out + nsplit - 1) / nsplit;
-    const int o0 = split * per, o1 = (o0 + per) < n_out ? (o0 + per) : n_out, cnt = o1 - o0;
+    int o0, cnt;  // this workgroup's slice of the head group's n_rep x D outputs: whole 8-element (16-byte bf16) groups
+    attn_merge_slice(n_rep * D, nsplit, split, &o0, &cnt);
     if (cnt > 0) {
-        const int q_first = o0 / D, q_last = (o1 - 1) / D;
-        // partials of the slice: element fastest across lanes (runs of consecutive d), all requested before any is used
-        constexpr int NLD = (NREP_MAX * D + 64 + 255) / 256;  // loads per thread for the largest slice x splits
-        float pr[NLD];
+        const int q_first = o0 / D, q_last = (o0 + cnt - 1) / D;
+        // partials of the slice in 16-byte sc1 loads -- 4 consecutive d of one (head, split), quad fastest across lanes -- all
+        // requested before any is used.  cnt / 4 quads x nsplit_tot splits <= 2 (n_rep 16 + nsplit - 1) <= 382 loads: two per thread.
+        constexpr int NLD = (2 * (NREP_MAX * 16 + 63) + 255) / 256;
+        const int nq4 = cnt >> 2;
+        u32x4 pr[NLD];
 #pragma unroll
         for (int k = 0; k < NLD; ++k) {
             const int idx = threadIdx.x + k * 256;
-            const int ii = idx % cnt, s2 = idx / cnt;
-            const int e = o0 + ii;
-            pr[k] = s2 < nsplit_tot ? ldf<true>(part_o + ((bh0 + e / D) * nsplit_tot + s2) * D + (e % D)) : 0.f;
+            const int e = o0 + (idx % nq4) * 4, s2 = idx / nq4;
+            pr[k] = load16_sc1(pors, s2 < nsplit_tot ? (uint32_t)(((e / D) * nsplit_tot + s2) * D + (e % D)) * 4 : O3V_OOB);
         }
         for (int q = q_first + wave; q <= q_last; q += 4) combine_weights<true>(part_ml, bh0 + q, nsplit_tot, sw + q * 64, sinv + q, lane);
-        const int ldp = nsplit_tot | 1;  // odd row stride: lanes on consecutive elements hit distinct banks
+        // pvt[split][element of the slice]: 16-byte writes and, below, lanes on consecutive elements -- both free of bank conflicts
 #pragma unroll
         for (int k = 0; k < NLD; ++k) {
             const int idx = threadIdx.x + k * 256;
-            const int ii = idx % cnt, s2 = idx / cnt;
-            if (s2 < nsplit_tot) pvt[ii * ldp + s2] = pr[k];
+            const int qi = idx % nq4, s2 = idx / nq4;
+            if (s2 < nsplit_tot) *reinterpret_cast<u32x4*>(pvt + s2 * cnt + qi * 4) = pr[k];
         }
         __syncthreads();
-        // per element the fmaf chain of combine_dim over the splits in order (its clamped tail terms have weight zero);
-        // eight LDS reads in flight per step of the chain
-        for (int ii = threadIdx.x; ii < cnt; ii += 256) {  // cnt <= 256 unless there are fewer splits than query heads
+        const __amdgpu_buffer_rsrc_t ars = __builtin_amdgcn_make_buffer_rsrc((void*)(ho.att_out + bh0 * D), 0, n_rep * D * 2, 0x00020000);
+        // per element the fmaf chain of combine_dim over the splits in order (its clamped tail terms have weight zero), one
+        // chain per thread, eight LDS reads in flight per step; then the bf16 results of eight neighbouring lanes are gathered
+        // into the first of them (cross-lane moves) and leave as one 16-byte sc1 store.  cnt % 8 == 0: a group of eight lanes
+        // is inside the slice or outside it as a whole, and every lane of the workgroup runs every trip.
+        for (int i0 = 0; i0 < cnt; i0 += 256) {  // one trip unless there are fewer splits than query heads
+            const bool in = i0 + (int)threadIdx.x < cnt;
+            const int ii = in ? i0 + (int)threadIdx.x : 0;
             const int e = o0 + ii, q = e / D;
-            const float* pp = pvt + ii * ldp;
+            const float* pp = pvt + ii;
             const float* ww = sw + q * 64;
             float acc = 0.f;
             for (int s0 = 0; s0 < nsplit_tot; s0 += 8) {
@@ -448,14 +479,17 @@ __device__ __forceinline__ void attn_decode_mfma_body(const bf16_t* __restrict__
 #pragma unroll
                 for (int u = 0; u < 8; ++u) {
                     const int s2 = s0 + u < nsplit_tot ? s0 + u : nsplit_tot - 1;
-                    pv8[u] = pp[s2];
+                    pv8[u] = pp[s2 * cnt];
                     w8[u] = s0 + u < nsplit_tot ? ww[s2] : 0.f;
                 }
 #pragma unroll
                 for (int u = 0; u < 8; ++u)
                     if (s0 + u < nsplit_tot) acc = fmaf(pv8[u], w8[u], acc);
             }
-            __hip_atomic_store(ho.att_out + bh0 * D + e, f2bf(acc * sinv[q]), O3V_RLX_AGENT);
+            const uint32_t r = f2bf(acc * sinv[q]);
+            const uint32_t p2 = r | ((uint32_t)__shfl_down(r, 1, 64) << 16);  // even lanes: elements e, e + 1
+            const u32x4 o8 = {p2, (uint32_t)__shfl_down(p2, 2, 64), (uint32_t)__shfl_down(p2, 4, 64), (uint32_t)__shfl_down(p2, 6, 64)};
+            if (in && (lane & 7) == 0) store16_sc1(ars, (uint32_t)e * 2, o8);
         }
     }
     // ---- ticket 2: the last slice tells every o_proj workgroup that this kv head's output is in memory

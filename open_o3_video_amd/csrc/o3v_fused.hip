@@ -709,6 +709,14 @@ extern "C" void o3v_fused_set_knob(int k) { g_knob = k; }
 
 extern "C" size_t o3v_decode_sync_bytes(void) { return (size_t)SYNC_WORDS * 4; }
 
+// the slice of a kv head's n_out = n_rep * D merged outputs that context split `split` of `nsplit` merges and publishes
+// (attn_merge_slice, the function the kernel calls; host-side for tests)
+extern "C" int o3v_attn_merge_slice(int n_out, int nsplit, int split, int* begin, int* count) {
+    if (!begin || !count || n_out <= 0 || (n_out & 7) || nsplit <= 0 || nsplit > 64 || split < 0 || split >= nsplit) return O3V_ERR_ARG;
+    attn_merge_slice(n_out, nsplit, split, begin, count);
+    return O3V_OK;
+}
+
 
 static int attn_block_launch(void* x, const void* ln_w, float eps, const void* qkv_w, const float* qkv_s, const void* qkv_b,
                              const void* o_w, const float* o_s, const void* q_norm, const void* k_norm, void* kv_raw,

@@ -362,6 +362,41 @@ __device__ __forceinline__ void gemv_body(const bf16_t* __restrict__ X, const bf
                 acc[r][m] = t;
             }
     }
+    if constexpr (PUB && EPI == EPI_QKVROPE) {
+        // The four waves of the workgroup own the rotary pairs j .. j+3 and j+D/2 .. j+D/2+3 of ONE head (D/2 % 4 == 0, N % 8 == 0:
+        // the launcher checks).  Eight element-wise write-through stores are eight fabric writes whose acknowledgements the drain
+        // before the ticket waits for: lane 0 of every wave leaves its two bf16 in LDS (the K-slice scratch, unused at KS == 1) and
+        // wave 0 publishes the workgroup's eight values as two 8-byte sc1 stores.  Same values as the element-wise epilogue below.
+        static_assert(M == 1 && R == 2 && KS == 1 && NW == 4 && NORM, "the packed q/k/v publish is written for the one-launch block's form");
+        uint16_t* ex = reinterpret_cast<uint16_t*>(smem + (size_t)M * K * 2);  // [2][4] bf16
+        const int half = ra.D >> 1, head = rows[0] / ra.D, j = rows[0] % ra.D;
+        if (lane == 0) {
+            float a0 = acc[0][0], a1 = acc[1][0];
+            if (WB == 1) {
+                a0 *= e_scale[0];
+                a1 *= e_scale[1];
+            }
+            const float v0 = rbf(a0 + e_bias[0]), v1 = rbf(a1 + e_bias[1]);
+            float o0 = v0, o1 = v1;  // v: no rotation
+            if (head < ra.Hq + ra.Hkv) {
+                const float c = e_cos[0], sn = e_sin[0];
+                o0 = __fadd_rn(rbf(__fmul_rn(v0, c)), rbf(__fmul_rn(-v1, sn)));
+                o1 = __fadd_rn(rbf(__fmul_rn(v1, c)), rbf(__fmul_rn(v0, sn)));
+            }
+            ex[wave] = f2bf(o0);
+            ex[4 + wave] = f2bf(o1);
+        }
+        __syncthreads();
+        if (wave == 0 && lane < 2 && rows[0] + 3 < N) {  // wave 0 owns pair j, j % 4 == 0: lane 0 stores j .. j+3, lane 1 j+D/2 .. j+D/2+3
+            bf16_t* dst = head < ra.Hq             ? ra.qout + (size_t)head * ra.D
+                          : head < ra.Hq + ra.Hkv ? ra.kc + ((size_t)(head - ra.Hq) * ra.Tmax + ra.slot) * ra.D
+                                                  : ra.vc + ((size_t)(head - ra.Hq - ra.Hkv) * ra.Tmax + ra.slot) * ra.D;
+            const u32x2 v = *reinterpret_cast<const u32x2*>(ex + lane * 4);
+            __hip_atomic_store(reinterpret_cast<uint64_t*>(dst + j + lane * half), (uint64_t)v[0] | ((uint64_t)v[1] << 32),
+                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // global_store_dwordx2 ... sc1
+        }
+        return;
+    }
     if (lane != 0) return;
     if (WB == 1) {
 #pragma unroll

@@ -64,6 +64,16 @@ __device__ __forceinline__ u32x4 load16_sc1(__amdgpu_buffer_rsrc_t rs, uint32_t 
 }
 constexpr uint32_t O3V_OOB = 0x7ffffff0u;
 
+// 16- and 8-byte write-through stores (buffer_store_dwordx4 / dwordx2 ... sc1): ONE fabric write per lane where element-wise sc1
+// stores cost one each (a dword store ~6x, a short store ~12x the time per byte of the 16-byte one).  An offset at or past the
+// descriptor's size stores nothing.
+__device__ __forceinline__ void store16_sc1(__amdgpu_buffer_rsrc_t rs, uint32_t byte_off, u32x4 v) {
+    __builtin_amdgcn_raw_buffer_store_b128(v, rs, byte_off, 0, 16);
+}
+__device__ __forceinline__ void store8_sc1(__amdgpu_buffer_rsrc_t rs, uint32_t byte_off, u32x2 v) {
+    __builtin_amdgcn_raw_buffer_store_b64(v, rs, byte_off, 0, 16);
+}
+
 template <bool SC1>
 __device__ __forceinline__ float ldf(const float* p) {
     return SC1 ? __hip_atomic_load(p, O3V_RLX_AGENT) : *p;

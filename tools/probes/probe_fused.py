@@ -4,7 +4,8 @@
 Diagnostic build only: `python tools/probes/probe_fused.py --build` (here, no GPU needed) compiles the library with
 -DO3V_STAMPS into open_o3_video_amd/libo3v_hip_stamps.so; on the GPU box the script loads that variant, runs decode-like
 steps at 7B dims (28 layers of distinct weights, so every launch streams cold weights; the MLP GEMVs run in between) and
-prints, for the last layer's launch, when each role's workgroups started, finished waiting and ended."""
+prints, for the last layer's launch, when each role's workgroups started, finished waiting and ended.
+`--lib PATH` loads another -DO3V_STAMPS build (variants of the kernel side by side), `--full-only` skips the ablations."""
 import argparse
 import ctypes as C
 import math
@@ -23,6 +24,8 @@ def main():
     ap.add_argument("--layers", type=int, default=28)
     ap.add_argument("--steps", type=int, default=6)
     ap.add_argument("--dims", default="7b", choices=["7b", "3b"])
+    ap.add_argument("--lib", default=VARIANT, help="another -DO3V_STAMPS build of the library (A/B of kernel variants)")
+    ap.add_argument("--full-only", action="store_true", help="timeline of the full kernel only, no ablations")
     args = ap.parse_args()
     from open_o3_video_amd import build as b
     if args.build:
@@ -31,7 +34,7 @@ def main():
     import numpy as np
     import torch
     from open_o3_video_amd import _lib
-    _lib.LIB_PATH = VARIANT
+    _lib.LIB_PATH = os.path.abspath(args.lib)
     lib = _lib.load()
     lib.o3v_fused_set_stamps.argtypes = [C.c_void_p]
     lib.o3v_fused_set_stamps.restype = None
@@ -127,9 +130,10 @@ def main():
     nb_qkv, nb_attn = N // 8, nsplit * Hkv
     roles = (("qkv", 0, nb_qkv), ("attn", nb_qkv, nb_qkv + nb_attn), ("o_proj", nb_qkv + nb_attn, grid))
     print(f"grid {grid}: qkv {nb_qkv} attn {nb_attn} o {grid - nb_qkv - nb_attn}; times in us from the first workgroup's start")
-    for knob, what in ((0, "full"), (1, "q/k/v role alone"), (2, "q/k/v + attention (o_proj role exits)"),
-                       (4, "no K/V request ahead of the wait"), (8, "o_proj weights after the wait"), (12, "neither"),
-                       (32, "o_proj weight stream paced: 1 x s_sleep 16 per step"), (64, "paced 2x"), (128, "paced 4x")):
+    knobs = ((0, "full"), (1, "q/k/v role alone"), (2, "q/k/v + attention (o_proj role exits)"),
+             (4, "no K/V request ahead of the wait"), (8, "o_proj weights after the wait"), (12, "neither"),
+             (32, "o_proj weight stream paced: 1 x s_sleep 16 per step"), (64, "paced 2x"), (128, "paced 4x"))
+    for knob, what in knobs[:1] if args.full_only else knobs:
         lib.o3v_fused_set_knob(knob)
         tl = timeit(step_fused, args.steps) if knob not in (1, 2) else float("nan")
         stamps.zero_()
@@ -155,6 +159,7 @@ def main():
             if name != "qkv":
                 print(f"{name:7s} wait over {stat(r[:, 1])}")
             if name == "attn":
+                print(f"{name:7s} computed  {stat(r[:, 6])}")   # partial arithmetic done, stores issued but not drained
                 print(f"{name:7s} partials  {stat(r[:, 2])}")
                 print(f"{name:7s} all known {stat(r[:, 4])}")
                 print(f"{name:7s} slice out {stat(r[:, 5])}")
