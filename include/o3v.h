@@ -374,6 +374,31 @@ int o3v_sample_step_ex(const void* logits, void* seen, int* cur_tok, int* finish
                        const int* eos_ids, int n_eos, int pad_id, int B, int V, int ldl, int do_sample, float rep_penalty,
                        float temperature, int top_k, float top_p, uint64_t seed, const int* row_id, int step, int out_stride,
                        float* scratch, const o3v_logprob_opts* lp, const o3v_sampling_opts* so, o3v_stream_t stream);
+/* Guided decoding, vLLM 0.7.2 SamplingParams(guided_decoding=GuidedDecodingParams(regex= | choice=)): the outlines-style logits
+ * processor (vllm/model_executor/guided_decoding/outlines_logits_processors.py BaseLogitsProcessor.__call__: mask = -inf
+ * everywhere, 0 at the token ids the FSM allows in the sequence's state; a restatement, parity unpinned) moved
+ * into the sampler passes, because a chunk of decode steps is enqueued without the host seeing a token.  The host compiles the
+ * pattern to a token-level automaton (open_o3_video_amd/guided.py); per row and step, in front of step 1 of o3v_sampling_opts:
+ *   0. x = -inf where next[q][i] < 0, q = state[step & 1][b]
+ * in every pass that forms processed scores (the sampling passes, both greedy stages, the log-prob passes: log-probs, ranks and
+ * top-N are those of the masked distribution).  The thread that stores the row's token also stores the row's next state,
+ * n = next[q][tok], as state[(step + 1) & 1][b] = (0 <= n < n_states) ? n : q -- the other half, so the log-prob launches of the
+ * step still read the state the token was drawn in.  A finished row keeps its state.  No launch is added.  The caller keeps every
+ * reachable state supplied with at least one token of finite score (guided.check_no_dead_end); the kernels clamp a state outside
+ * [0, n_states) into it. */
+typedef struct {
+    const int16_t* next;  /* i16 [n_states, ldn], 16-byte aligned; next[q][t] < 0: token t is not allowed in state q */
+    int n_states, ldn;    /* ldn >= vocab, ldn % 8 == 0 */
+    int* state;           /* i32 [2, B]: row b's state at decode step s is state[s & 1][b]; the step's last stage writes state[(s+1) & 1][b] */
+} o3v_guided_opts;
+/* o3v_sample_step_ex plus the guide.  go == NULL is o3v_sample_step_ex exactly (`so` required then).  With a guide `so` may be
+ * NULL: a zeroed control set.  O3V_ERR_ARG before any launch for what o3v_sample_step_ex refuses and for: next or state NULL, next
+ * not 16-byte or state not 4-byte aligned, n_states <= 0 (or > 32767), ldn < V or ldn % 8 != 0. */
+int o3v_sample_step_guided(const void* logits, void* seen, int* cur_tok, int* finished, int* out_ids, float* margins,
+                           const int* eos_ids, int n_eos, int pad_id, int B, int V, int ldl, int do_sample, float rep_penalty,
+                           float temperature, int top_k, float top_p, uint64_t seed, const int* row_id, int step, int out_stride,
+                           float* scratch, const o3v_logprob_opts* lp, const o3v_sampling_opts* so, const o3v_guided_opts* go,
+                           o3v_stream_t stream);
 /* Prompt side (vLLM prompt_logprobs; R:grpo_trainer.py:371-384 for the target log-prob): the same selection on raw logits (no
  * penalty, temperature 1, no masks) of R <= 65535 rows; row r predicts target[r].  Outputs [R] and [R, n]. */
 #define O3V_LOGPROB_ROW_SCRATCH_FLOATS 384 /* per row */
@@ -627,6 +652,13 @@ int o3v_llm_decode_lp(const o3v_llm_desc* d, const o3v_decode_state* st, const o
  * checks it, before anything else. */
 int o3v_llm_decode_ex(const o3v_llm_desc* d, const o3v_decode_state* st, const o3v_logprob_opts* lp, const o3v_sampling_opts* so,
                       int step0, int n_steps, int skip_last_forward, o3v_stream_t stream);
+/* The same with a guide (o3v_guided_opts; vLLM's guided-decoding logits processor run inside the sampler): go == NULL is
+ * o3v_llm_decode_ex exactly (same launches, same ids).  Otherwise every step runs the extended sampler kernels (no added launch; on
+ * a zeroed control set when `so` is NULL) masked by the state of go->state's half `step & 1`, and its last stage writes the other
+ * half; scratch and B <= 32 as o3v_llm_decode_ex asks with `so`.  `so` and `go` are checked as o3v_sample_step_guided checks them
+ * (ldn against d->vocab), before anything else. */
+int o3v_llm_decode_guided(const o3v_llm_desc* d, const o3v_decode_state* st, const o3v_logprob_opts* lp, const o3v_sampling_opts* so,
+                          const o3v_guided_opts* go, int step0, int n_steps, int skip_last_forward, o3v_stream_t stream);
 
 /* ---- in-place weight update (vLLM / TRL model.load_weights after each optimizer step; R:grpo_trainer.py:581-586 generates
  * from the weights being trained) ------------------------------------------------------------------------------------------ */

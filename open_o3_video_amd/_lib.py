@@ -83,6 +83,11 @@ class SamplingOpts(C.Structure):
                 ("out_counts", vp)]
 
 
+class GuidedOpts(C.Structure):
+    """o3v_guided_opts: the token-level automaton of a guide (i16 [n_states, ldn]) and the rows' double-buffered states."""
+    _fields_ = [("next", vp), ("n_states", i32), ("ldn", i32), ("state", vp)]
+
+
 class PrefillOpts(C.Structure):
     _fields_ = [("ds_rows", vp), ("ds_src", vp), ("n_ds", i32), ("ds_feat", vp), ("n_deep", i32), ("ds_stride", i64),
                 ("kprefix", vp), ("vprefix", vp), ("prefix_len", i32), ("prefix_cap", i32), ("rows_per_prefix", i32), ("w8a8", i32)]
@@ -183,6 +188,10 @@ SIGNATURES = {
                            C.POINTER(LogprobOpts), C.POINTER(SamplingOpts), vp],
     "o3v_llm_decode_ex": [C.POINTER(LlmDesc), C.POINTER(DecodeStateOwn), C.POINTER(LogprobOpts), C.POINTER(SamplingOpts), i32, i32, i32,
                           vp],
+    "o3v_sample_step_guided": [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, f32, i32, f32, u64, vp, i32, i32, vp,
+                               C.POINTER(LogprobOpts), C.POINTER(SamplingOpts), C.POINTER(GuidedOpts), vp],
+    "o3v_llm_decode_guided": [C.POINTER(LlmDesc), C.POINTER(DecodeStateOwn), C.POINTER(LogprobOpts), C.POINTER(SamplingOpts),
+                              C.POINTER(GuidedOpts), i32, i32, i32, vp],
 }
 _RET = {"o3v_ctx_create": vp, "o3v_ctx_destroy": None, "o3v_ctx_llm": C.POINTER(LlmDesc), "o3v_ctx_vit": C.POINTER(VitDesc),
         "o3v_ctx_vit3": C.POINTER(Vit3Desc), "o3v_vit_workspace_bytes": sz, "o3v_vit3_workspace_bytes": sz, "o3v_llm_workspace_bytes": sz, "o3v_decode_sync_bytes": sz}

@@ -169,7 +169,31 @@ struct o3v_samp_x {
     uint16_t* cnt_prev;  // u16 [B]: the emitted token's count before this step counted it (the log-prob pass needs it)
     float pres, freq;    // presence / frequency penalty
     unsigned minp_bits;  // bit pattern of min_p (0: off)
+    // guided decoding (o3v_guided_opts resolved for this step; g_next NULL: no guide)
+    const int16_t* g_next;  // i16 [g_n, g_ldn] token-level automaton: g_next[q][t] < 0 masks token t in state q; 16-byte aligned rows
+    const int* g_q;         // i32 [B]: the states every pass of this step reads
+    int* g_qn;              // i32 [B]: the states the step's last stage writes (the other half of the double buffer)
+    int g_n, g_ldn;
 };
+// the row of the guide's table that masks row b at this step (NULL: no guide); a state outside the table is clamped into it
+__device__ __forceinline__ int o3v_guide_state(const o3v_samp_x& x, int b) {
+    const int q = x.g_q[b];
+    return q < 0 ? 0 : (q >= x.g_n ? x.g_n - 1 : q);
+}
+__device__ __forceinline__ const int16_t* o3v_guide_row(const o3v_samp_x& x, int b) {
+    return x.g_next ? x.g_next + (size_t)o3v_guide_state(x, b) * x.g_ldn : nullptr;
+}
+// last sampler stage: the automaton follows the token an unfinished row emits; a finished row keeps its state
+__device__ __forceinline__ void o3v_guide_advance(const o3v_samp_x& x, int b, int V, int tok, bool fin) {
+    if (!x.g_next) return;
+    const int q = o3v_guide_state(x, b);
+    int n = q;
+    if (!fin && tok >= 0 && tok < V) {
+        const int t = x.g_next[(size_t)q * x.g_ldn + tok];
+        if (t >= 0 && t < x.g_n) n = t;
+    }
+    x.g_qn[b] = n;
+}
 // last sampler stage: count the token an unfinished row emits (saturating), leave its earlier count for the log-probs
 __device__ __forceinline__ void o3v_count_token(const o3v_samp_x& x, int b, int V, int tok, bool fin) {
     uint16_t c = 0;

@@ -675,7 +675,7 @@ __device__ __forceinline__ void top2_merge(float& best, int& bi, float& second, 
 
 // stage 1: grid (NB, B) x 256 threads, each block reduces a contiguous slice of the vocabulary to (best, idx, second).
 // EX (the `_x` entry): the static edits are added before the repetition penalty and the count penalties follow it
-// (o3v_sampling_opts; the same arithmetic as o3v_sample.hip's load_group)
+// (o3v_sampling_opts; the same arithmetic as o3v_sample.hip's load_group), and a guide masks in front of both (o3v_guided_opts)
 template <bool EX>
 __device__ __forceinline__ void sample_greedy_partial_body(const bf16_t* __restrict__ logits, const uint8_t* __restrict__ seen,
                                                            float* __restrict__ part, int V, int ldl, float rep_penalty,
@@ -685,11 +685,13 @@ __device__ __forceinline__ void sample_greedy_partial_body(const bf16_t* __restr
     const uint8_t* sr = seen + (size_t)b * V;
     const float* bias = EX ? sx.bias : nullptr;
     const uint16_t* cr = (EX && sx.counts) ? sx.counts + (size_t)b * V : nullptr;
+    const int16_t* gr = EX ? o3v_guide_row(sx, b) : nullptr;   // negative next state: the token is masked
     const int per = (V + GREEDY_NB - 1) / GREEDY_NB;
     const int i0 = nb * per, i1 = (i0 + per < V) ? i0 + per : V;
     float best = -INFINITY, second = -INFINITY;
     int bi = 0x7fffffff;
-    auto visit = [&](int i, float s, unsigned seen_byte, float bias_i = 0.f, unsigned c = 0) {
+    auto visit = [&](int i, float s, unsigned seen_byte, float bias_i = 0.f, unsigned c = 0, bool masked = false) {
+        if (EX && masked) s = -INFINITY;
         if (EX && bias) s += bias_i;
         if (rep_penalty != 1.0f && seen_byte) s = (s < 0.f) ? s * rep_penalty : s / rep_penalty;
         if (EX && c) s = s - (sx.freq * (float)c + sx.pres);
@@ -717,11 +719,13 @@ __device__ __forceinline__ void sample_greedy_partial_body(const bf16_t* __restr
                     bv[0] = b0.x, bv[1] = b0.y, bv[2] = b0.z, bv[3] = b0.w, bv[4] = b1.x, bv[5] = b1.y, bv[6] = b1.z, bv[7] = b1.w;
                 }
                 if (cr) cv = *reinterpret_cast<const uint4*>(cr + g * 8);
-                const uint32_t cw[4] = {cv.x, cv.y, cv.z, cv.w};
+                uint4 gv = {0u, 0u, 0u, 0u};
+                if (gr) gv = *reinterpret_cast<const uint4*>(gr + g * 8);
+                const uint32_t cw[4] = {cv.x, cv.y, cv.z, cv.w}, gw[4] = {gv.x, gv.y, gv.z, gv.w};
 #pragma unroll
                 for (int k = 0; k < 8; ++k)
                     visit(g * 8 + k, (k & 1) ? bf_hi(lw[k >> 1]) : bf_lo(lw[k >> 1]), ((k < 4 ? sv.x : sv.y) >> (8 * (k & 3))) & 0xffu,
-                          bv[k], (cw[k >> 1] >> (16 * (k & 1))) & 0xffffu);
+                          bv[k], (cw[k >> 1] >> (16 * (k & 1))) & 0xffffu, ((gw[k >> 1] >> (16 * (k & 1))) & 0x8000u) != 0);
                 continue;
             }
 #pragma unroll
@@ -729,7 +733,7 @@ __device__ __forceinline__ void sample_greedy_partial_body(const bf16_t* __restr
                 visit(g * 8 + k, (k & 1) ? bf_hi(lw[k >> 1]) : bf_lo(lw[k >> 1]), ((k < 4 ? sv.x : sv.y) >> (8 * (k & 3))) & 0xffu);
         }
     } else if (EX) {
-        for (int i = i0 + threadIdx.x; i < i1; i += 256) visit(i, bf2f(lr[i]), sr[i], bias ? bias[i] : 0.f, cr ? cr[i] : 0u);
+        for (int i = i0 + threadIdx.x; i < i1; i += 256) visit(i, bf2f(lr[i]), sr[i], bias ? bias[i] : 0.f, cr ? cr[i] : 0u, gr && gr[i] < 0);
     } else {
         for (int i = i0 + threadIdx.x; i < i1; i += 256) visit(i, bf2f(lr[i]), sr[i]);
     }
@@ -796,6 +800,7 @@ __device__ __forceinline__ void sample_greedy_final_body(const float* __restrict
     if (lane == 0) {
         int tok = finished[b] ? pad_id : bi;
         if (EX && sx.counts) o3v_count_token(sx, b, V, tok, finished[b] != 0);
+        if (EX) o3v_guide_advance(sx, b, V, tok, finished[b] != 0);
         if (!finished[b]) {
             for (int k = 0; k < n_eos; ++k)
                 if (tok == eos_ids[k]) finished[b] = 1;

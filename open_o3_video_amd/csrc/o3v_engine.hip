@@ -435,6 +435,7 @@ int o3v_sample_lp_step(const void* logits, void* seen, int* cur_tok, int* finish
                        float top_p, uint64_t seed, const int* row_id, int step, int out_stride, float* scratch, const void* embed,
                        void* x_out, int hidden, const o3v_logprob_opts* lp, const o3v_samp_x* sx, hipStream_t stream);
 int o3v_sampling_resolve(const o3v_sampling_opts* so, int step, o3v_samp_x* x);
+int o3v_guided_resolve(const o3v_guided_opts* go, int B, int V, int step, o3v_samp_x* x);
 
 extern "C" int o3v_llm_decode(const o3v_llm_desc* d, const o3v_decode_state* st, int step0, int n_steps,
                               int skip_last_forward, o3v_stream_t s) {
@@ -531,11 +532,15 @@ struct Decode {
     int kv_cap() const { return r.kv8 ? 1 : st->Tmax; }
     uint32_t epoch(int l) const { return (uint32_t)(step * d->layers + l + 1); }  // of the one-launch forms
     bool first(int l) const { return l == 0 && step == step0; }                   // the launch at which settle() may switch a form off
-    int sample(const o3v_logprob_opts* lp, const o3v_sampling_opts* so) {
+    int sample(const o3v_logprob_opts* lp, const o3v_sampling_opts* so, const o3v_guided_opts* go) {
         // so: the extended sampler kernels on this step's controls, then (lp given) its log-probs
         // lp alone: the same sampler, then the log-probs of what it drew (sampling: the embedding row is gathered below as usual)
+        // go: the extended kernels with the guide's mask and state (on a zeroed control set when so is NULL)
+        static const o3v_sampling_opts plain = {};
+        if (go && !so) so = &plain;
         o3v_samp_x sx;
         if (so) TRY(o3v_sampling_resolve(so, step, &sx));
+        if (go) TRY(o3v_guided_resolve(go, B, V, step, &sx));
         if (so || lp)
             return o3v_sample_lp_step(st->logits, st->seen, st->cur_tok, st->finished, st->out_ids, st->margins, st->eos_ids, st->n_eos,
                                       st->pad_id, B, V, V, st->do_sample, st->rep_penalty, st->temperature, st->top_k, st->top_p, st->seed,
@@ -676,8 +681,15 @@ struct Decode {
 
 extern "C" int o3v_llm_decode_ex(const o3v_llm_desc* d, const o3v_decode_state* st, const o3v_logprob_opts* lp,
                                  const o3v_sampling_opts* so, int step0, int n_steps, int skip_last_forward, o3v_stream_t s) {
+    return o3v_llm_decode_guided(d, st, lp, so, nullptr, step0, n_steps, skip_last_forward, s);
+}
+
+extern "C" int o3v_llm_decode_guided(const o3v_llm_desc* d, const o3v_decode_state* st, const o3v_logprob_opts* lp,
+                                     const o3v_sampling_opts* so, const o3v_guided_opts* go, int step0, int n_steps,
+                                     int skip_last_forward, o3v_stream_t s) {
     o3v_samp_x probe;
     if (so) TRY(o3v_sampling_resolve(so, 0, &probe));  // host-only checks of the controls, before anything else
+    if (go) TRY(o3v_guided_resolve(go, 0, d ? d->vocab : 0, 0, &probe));   // (d NULL is refused below)
     if (!d || !st || !st->x || !st->kcache || !st->vcache || !st->cosT || !st->sinT || !st->logits || !st->seen ||
         !st->cur_tok || !st->finished || !st->out_ids || !st->part_o || !st->part_ml || !st->workspace || !st->sample_scratch)
         return O3V_ERR_ARG;
@@ -703,7 +715,7 @@ extern "C" int o3v_llm_decode_ex(const o3v_llm_desc* d, const o3v_decode_state* 
     c.pre_stride = pfx ? (size_t)(B / st->rows_per_prompt) * c.Hkv * st->prefix_cap * c.D * 2 : 0;
     for (int i = 0; i < n_steps; ++i) {
         c.step = step0 + i;
-        TRY(c.sample(lp, so));
+        TRY(c.sample(lp, so, go));
         if (skip_last_forward && i == n_steps - 1) break;
         if (c.slot0 + c.step >= st->Tmax) return O3V_ERR_ARG;
         // one decode forward: token `step` sits in cache slot S+step, context = S+step+1 keys

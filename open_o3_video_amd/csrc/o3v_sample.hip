@@ -103,6 +103,7 @@ struct Row {
     const float* bias;
     const uint16_t* cr;
     float pres, freq;
+    const int16_t* gr;   // the guide's table row of this row's state (negative entry: the token is masked) or NULL
 };
 
 template <bool EX = false>
@@ -113,6 +114,7 @@ __device__ __forceinline__ Row make_row(const bf16_t* logits, const uint8_t* see
     r.cr = (EX && x.counts) ? x.counts + (size_t)b * V : nullptr;
     r.pres = EX ? x.pres : 0.f;
     r.freq = EX ? x.freq : 0.f;
+    r.gr = EX ? o3v_guide_row(x, b) : nullptr;
     r.lr = logits + (size_t)b * ldl;
     r.sr = seen + (size_t)b * V;
     r.V = V;
@@ -127,7 +129,8 @@ __device__ __forceinline__ Row make_row(const bf16_t* logits, const uint8_t* see
 __device__ __forceinline__ float count_penalty(float x, unsigned c, float pres, float freq) { return x - (freq * (float)c + pres); }
 
 // processed scores of elements 8g..8g+7 (TF:404-414 penalty, :301-303 temperature); -inf past the vocabulary.
-// EX: the static edits are added first and the count penalties follow the repetition penalty (vLLM 0.7.2 V0 sampler order).
+// EX: the static edits are added first and the count penalties follow the repetition penalty (vLLM 0.7.2 V0 sampler order); a guide
+// masks before all of them (vLLM runs guided decoding as a logits processor): eight i16 next-states beside the counts.
 template <bool EX = false>
 __device__ __forceinline__ void load_group(const Row& r, int g, float s[8]) {
     const int base = g * 8;
@@ -141,10 +144,13 @@ __device__ __forceinline__ void load_group(const Row& r, int g, float s[8]) {
             bv[0] = b0.x, bv[1] = b0.y, bv[2] = b0.z, bv[3] = b0.w, bv[4] = b1.x, bv[5] = b1.y, bv[6] = b1.z, bv[7] = b1.w;
         }
         if (EX && r.cr) cv = *reinterpret_cast<const u32x4*>(r.cr + base);
+        u32x4 gv = {0u, 0u, 0u, 0u};
+        if (EX && r.gr) gv = *reinterpret_cast<const u32x4*>(r.gr + base);
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
             float x = bf2f((bf16_t)((lv[k >> 1] >> (16 * (k & 1))) & 0xffffu));
             const unsigned sb = ((k < 4 ? sv.x : sv.y) >> (8 * (k & 3))) & 0xffu;
+            if (EX && ((gv[k >> 1] >> (16 * (k & 1))) & 0x8000u)) x = -INFINITY;   // next state < 0
             if (EX && r.bias) x += bv[k];
             if (r.rep != 1.0f && sb) x = (x < 0.f) ? x * r.rep : x / r.rep;
             if (EX) {
@@ -160,6 +166,7 @@ __device__ __forceinline__ void load_group(const Row& r, int g, float s[8]) {
             float x = -INFINITY;
             if (i < r.V) {
                 x = bf2f(r.lr[i]);
+                if (EX && r.gr && r.gr[i] < 0) x = -INFINITY;
                 if (EX && r.bias) x += r.bias[i];
                 if (r.rep != 1.0f && r.sr[i]) x = (x < 0.f) ? x * r.rep : x / r.rep;
                 if (EX && r.cr) {
@@ -501,6 +508,7 @@ __device__ __forceinline__ void sample_draw_body(const bf16_t* __restrict__ logi
         if (seen_prev) seen_prev[b] = (tok >= 0 && tok < V) ? seen[(size_t)b * V + tok] : 0;  // log-probs see the map before this step
         if (tok >= 0 && tok < V) seen[(size_t)b * V + tok] = 1;
         if (EX && x.counts) o3v_count_token(x, b, V, tok, fin);
+        if (EX) o3v_guide_advance(x, b, V, tok, fin);
         cur_tok[b] = tok;
         out_ids[(size_t)b * out_stride + step] = tok;
         if (chosen_lp) chosen_lp[(size_t)b * out_stride + step] = logf(e_pick / ((float)ws[WS_Z] * (1.0f / FX_SCALE)));
@@ -602,6 +610,7 @@ __device__ __forceinline__ float lp_token_score(const bf16_t* lr, int tok, int V
                                                 float temp, const SampX& sx = SampX{}) {
     if (tok < 0 || tok >= V) return -INFINITY;
     float x = bf2f(lr[tok]);
+    if (EX && sx.g_next && o3v_guide_row(sx, b)[tok] < 0) x = -INFINITY;   // (the state of before the step: the draw wrote the other half)
     if (EX && sx.bias) x += sx.bias[tok];
     if (seen_prev && rep != 1.0f && seen_prev[b]) x = (x < 0.f) ? x * rep : x / rep;
     if (EX && sx.counts && sx.cnt_prev) {
@@ -642,6 +651,7 @@ __device__ __forceinline__ void lp_partial_body(const bf16_t* __restrict__ logit
     r.cr = (EX && sx.counts) ? sx.counts + (size_t)b * V : nullptr;
     r.pres = EX ? sx.pres : 0.f;
     r.freq = EX ? sx.freq : 0.f;
+    r.gr = EX ? o3v_guide_row(sx, b) : nullptr;
     KeptTest kept_test{0.f, 0u, 0u};
     if (SAMPLED) {
         const u64* ws = wsp + (size_t)b * (WS_FLOATS / 2);
@@ -983,6 +993,25 @@ int o3v_sampling_resolve(const o3v_sampling_opts* so, int step, o3v_samp_x* x) {
     unsigned bits;
     memcpy(&bits, &so->min_p, 4);
     x->minp_bits = bits;
+    x->g_next = nullptr;
+    x->g_q = nullptr;
+    x->g_qn = nullptr;
+    x->g_n = x->g_ldn = 0;
+    return O3V_OK;
+}
+
+// o3v_guided_opts -> the guide of decode step `step` of B rows over V tokens (V <= 0: the vocabulary is not known yet, the caller
+// checks ldn against it later); O3V_ERR_ARG for what the header rules out (host only, before any launch)
+int o3v_guided_resolve(const o3v_guided_opts* go, int B, int V, int step, o3v_samp_x* x) {
+    if (!go || !x || step < 0 || B < 0) return O3V_ERR_ARG;
+    if (!go->next || !go->state || (reinterpret_cast<uintptr_t>(go->next) & 15) || (reinterpret_cast<uintptr_t>(go->state) & 3))
+        return O3V_ERR_ARG;
+    if (go->n_states <= 0 || go->n_states > 32767 || go->ldn <= 0 || (go->ldn & 7) || (V > 0 && go->ldn < V)) return O3V_ERR_ARG;
+    x->g_next = go->next;
+    x->g_n = go->n_states;
+    x->g_ldn = go->ldn;
+    x->g_q = go->state + (size_t)(step & 1) * B;
+    x->g_qn = go->state + (size_t)((step + 1) & 1) * B;
     return O3V_OK;
 }
 
@@ -993,6 +1022,26 @@ extern "C" int o3v_sample_step_ex(const void* logits, void* seen, int* cur_tok, 
                                   hipStream_t stream) {
     o3v_samp_x x;
     const int rc = o3v_sampling_resolve(so, step, &x);
+    if (rc != O3V_OK) return rc;
+    return o3v_sample_lp_step(logits, seen, cur_tok, finished, out_ids, margins, eos_ids, n_eos, pad_id, B, V, ldl, do_sample,
+                              rep_penalty, temperature, top_k, top_p, seed, row_id, step, out_stride, scratch, nullptr, nullptr, 0, lp,
+                              &x, stream);
+}
+
+extern "C" int o3v_sample_step_guided(const void* logits, void* seen, int* cur_tok, int* finished, int* out_ids, float* margins,
+                                      const int* eos_ids, int n_eos, int pad_id, int B, int V, int ldl, int do_sample, float rep_penalty,
+                                      float temperature, int top_k, float top_p, uint64_t seed, const int* row_id, int step,
+                                      int out_stride, float* scratch, const o3v_logprob_opts* lp, const o3v_sampling_opts* so,
+                                      const o3v_guided_opts* go, hipStream_t stream) {
+    if (!go)
+        return o3v_sample_step_ex(logits, seen, cur_tok, finished, out_ids, margins, eos_ids, n_eos, pad_id, B, V, ldl, do_sample,
+                                  rep_penalty, temperature, top_k, top_p, seed, row_id, step, out_stride, scratch, lp, so, stream);
+    const o3v_sampling_opts plain = {};   // a guide alone: the extended kernels on a zeroed control set
+    o3v_samp_x x;
+    int rc = o3v_sampling_resolve(so ? so : &plain, step, &x);
+    if (rc != O3V_OK) return rc;
+    if (V <= 0) return O3V_ERR_ARG;
+    rc = o3v_guided_resolve(go, B, V, step, &x);
     if (rc != O3V_OK) return rc;
     return o3v_sample_lp_step(logits, seen, cur_tok, finished, out_ids, margins, eos_ids, n_eos, pad_id, B, V, ldl, do_sample,
                               rep_penalty, temperature, top_k, top_p, seed, row_id, step, out_stride, scratch, nullptr, nullptr, 0, lp,

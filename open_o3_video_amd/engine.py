@@ -19,7 +19,7 @@ from typing import NamedTuple, Optional, Sequence
 import numpy as np
 import torch
 
-from . import _lib, indexing
+from . import _lib, guided, indexing
 from .config import O3VConfig
 from .weights import DeviceWeights
 
@@ -174,7 +174,7 @@ class _DecodeBuffers:
     The structs hold bare addresses, so this object lives until the last o3v_llm_decode_ex call and the final check_waits()."""
 
     def __init__(self, eng: "O3VEngine", plan: DecodePlan, S, T, G, ids_rep, pad_rep, eos_token_ids, row_ids, return_margins, n_lp,
-                 sampling, knobs, cosd, sind, logits, kc, vc, kc0, vc0, kv8=None, kv8_emulate=False, own=None):
+                 sampling, knobs, cosd, sind, logits, kc, vc, kc0, vc0, kv8=None, kv8_emulate=False, own=None, guide=None):
         tc, dev = eng.cfg.text, eng.dev
         B, V = plan.B, tc.vocab_size
         zeros = lambda shape, dtype: torch.zeros(shape, dtype=dtype, device=dev)
@@ -198,7 +198,15 @@ class _DecodeBuffers:
         n_rep_total = B * tc.num_attention_heads
         self.part_o = empty(n_rep_total * 64 * tc.head_dim, torch.float32)
         self.part_ml = empty(n_rep_total * 64 * 2, torch.float32)
-        self.scratch = empty((B, _lib.SAMPLE_SCRATCH_FLOATS if knobs["do_sample"] or n_lp or sampling else 256), torch.float32)
+        self.scratch = empty((B, _lib.SAMPLE_SCRATCH_FLOATS if knobs["do_sample"] or n_lp or sampling or guide is not None else 256),
+                             torch.float32)
+        # guided decoding: the rows' automaton states, double-buffered (step s reads half s & 1, its last stage writes the other)
+        self.guide = self.go = self.guide_state = None
+        if guide is not None:
+            self.guide = guide      # keeps the device table alive
+            self.guide_state = torch.full((2, B), int(guide.start), dtype=torch.int32, device=dev)
+            self.go = _lib.GuidedOpts(next=guide.table.data_ptr(), n_states=int(guide.n_states), ldn=int(guide.ldn),
+                                      state=self.guide_state.data_ptr())
         self.so = None
         if sampling:    # the extended sampler kernels: static-edit vectors and (penalties only) the u16 output counts
             self.bias, self.early = (None if v is None else torch.from_numpy(v).to(dev)
@@ -619,7 +627,7 @@ class O3VEngine:
                  second_per_grid_ts=None, logprobs: int = 0, prompt_logprobs: int = 0, min_p: float = 0.0,
                  presence_penalty: float = 0.0, frequency_penalty: float = 0.0, min_new_tokens: int = 0, token_bias=None,
                  allowed_token_ids=None, banned_token_ids=None, stop_checker=None, shared_prefix_len: Optional[int] = None,
-                 _fused_ok: bool = True) -> GenerateOutput:
+                 guide=None, _fused_ok: bool = True) -> GenerateOutput:
         """HF-semantics generate.  `num_return_sequences=G` shares ONE ViT pass and ONE prefill across the G
         completions of a prompt (the reference recomputes both G times, TF:1493-1579) and fans the KV cache out.
 
@@ -651,7 +659,15 @@ class O3VEngine:
         cache holds its suffix, left-padded to the longest, and its generated tokens (indexing.shared_prefix_layout, plan_decode's
         `suffix`).  A mismatch raises ValueError.  Shapes the group kernels do not serve (head_dim != 128, one row, more than 32
         own-key splits, prompt_logprobs, group_attention off) run as independent rows on the replicated visual inputs;
-        timings["shared_prefix_rows"] tells which ran (rows in the group, 0 = independent rows)."""
+        timings["shared_prefix_rows"] tells which ran (rows in the group, 0 = independent rows).
+
+        `guide` (guided.Guide; vLLM guided_decoding regex / choice): a token-level automaton on the device,
+        i16 [n_states, ldn] with ldn >= vocabulary and ldn % 8 == 0.  Every row starts in `guide.start`; at each step the tokens
+        whose entry in the row's state is negative are masked inside the sampler passes, in front of every other control, and the
+        sampler's last stage moves the row to the entry of the token it emits -- no host round trip, no added launch, every decode
+        regime.  The table is checked against the call's static bias first (guided.check_no_dead_end); `min_new_tokens` > 0 is
+        refused with a guide (an accepting state whose only token is EOS would have none).  timings["guide_states"] holds the
+        rows' states after the last step."""
         cfg, tc = self.cfg, self.cfg.text
         ids, mask, pad = prompt_arrays(input_ids, attention_mask)
         B0, S = ids.shape
@@ -669,6 +685,8 @@ class O3VEngine:
                 raise ValueError(f"`{what}` must be in 0..{_lib.MAX_LOGPROBS}, got {v}")
         sampling = self._sampling_vectors(tc.vocab_size, T, eos_token_ids, bool(do_sample), min_p, presence_penalty, frequency_penalty,
                                           min_new_tokens, token_bias, allowed_token_ids, banned_token_ids)
+        if guide is not None:
+            self._check_guide(guide, tc.vocab_size, sampling, min_new_tokens)
         nsplit_env = os.environ.get("O3V_NSPLIT")      # A/B switch (tools/probes), read at every call
         if self.kv_cache_dtype not in ("bf16", "fp8"):
             raise ValueError(f"kv_cache_dtype={self.kv_cache_dtype!r}: 'bf16' or 'fp8'")
@@ -754,7 +772,7 @@ class O3VEngine:
         knobs = dict(pad_id=pad_id, n_eos=len(eos_token_ids), do_sample=int(do_sample), rep_penalty=float(repetition_penalty),
                      temperature=float(temperature), top_p=float(top_p), seed=int(seed) & (2 ** 64 - 1), top_k=max(0, int(top_k or 0)))
         buf = _DecodeBuffers(self, plan, state["S"], T, state["G"], ids_rep, state["pad_rep"], eos_token_ids, row_ids, return_margins,
-                             n_lp, sampling, knobs, cosd, sind, logits, kc, vc, kc0, vc0, kv8, emulate, own=state["own"])
+                             n_lp, sampling, knobs, cosd, sind, logits, kc, vc, kc0, vc0, kv8, emulate, own=state["own"], guide=guide)
         tm["kv_cache_dtype"] = kv_dtype
         tm["kv_cache_bytes"] = int((kc.numel() + vc.numel() + (kc0.numel() + vc0.numel() if plan.shared_prompt else 0)) * 2 +
                                    sum(t.numel() * t.element_size() for t in kv8 or ()))
@@ -767,6 +785,8 @@ class O3VEngine:
         tm["launches_per_layer"] = (stats[1] / layers_run) if layers_run else None
         tm["fused_attention_layers"], tm["standalone_attention_layers"] = int(stats[2]), int(stats[3])
         buf.check_waits()
+        if guide is not None:       # step `done` would read half done & 1
+            tm["guide_states"] = buf.guide_state[done & 1].cpu().tolist()
         if getattr(self, "_debug_keep", False):     # probe hook: the decode's state after the last step
             self._debug_last = {"kc": kc, "vc": vc, "logits": logits, "x": buf.x, "S": state["S"], "cos": cosd, "sin": sind, "k_lo": buf.k_lo,
                                 "nsplit": plan.nsplit, "Tmax": plan.Tmax, "out_ids": buf.out_ids,
@@ -925,14 +945,18 @@ class O3VEngine:
         """Chunks of decode steps enqueued from C++, one host check per chunk (TF:utils.py:2936-2937) -> (steps done, ended: rows
         the stop checker ended -> number of tokens they keep)."""
         B, pad_id = buf.st.B, buf.st.pad_id
-        lp_opts, so = (None if o is None else C.byref(o) for o in (buf.lp_opts, buf.so))
+        lp_opts, so, go = (None if o is None else C.byref(o) for o in (buf.lp_opts, buf.so, buf.go))
         done = 0
         chunk = max(1, int(steps_per_sync)) if (use_eos or stop_checker is not None) else T
         ended = {}
         while done < T:
             # the first chunk is short whenever the one-launch block is in use: its time-out word is read right after it
             n = min(chunk if (done or buf.sync is None) else min(chunk, getattr(self, "_first_chunk", 16)), T - done)
-            _lib.call("o3v_llm_decode_ex", C.byref(self.w.llm), C.byref(buf.st), lp_opts, so, done, n, int(done + n == T), _stream())
+            if go is None:
+                _lib.call("o3v_llm_decode_ex", C.byref(self.w.llm), C.byref(buf.st), lp_opts, so, done, n, int(done + n == T), _stream())
+            else:
+                _lib.call("o3v_llm_decode_guided", C.byref(self.w.llm), C.byref(buf.st), lp_opts, so, go, done, n, int(done + n == T),
+                          _stream())
             first = done == 0
             done += n
             if first and done < T:
@@ -950,6 +974,20 @@ class O3VEngine:
             if (use_eos or ended) and done < T and bool(buf.finished.all().item()):
                 break
         return done, ended
+
+    def _check_guide(self, guide, V: int, sampling, min_new_tokens):
+        """generate(guide=...): the table's shape and device, min_new_tokens, and no dead end under the call's static bias."""
+        t = guide.table
+        if not (torch.is_tensor(t) and t.dtype == torch.int16 and t.dim() == 2 and t.is_contiguous() and t.is_cuda):
+            raise ValueError("guide.table must be a contiguous int16 tensor [n_states, ldn] on the engine's device")
+        n, ldn = int(t.shape[0]), int(t.shape[1])
+        if (n, ldn) != (int(guide.n_states), int(guide.ldn)) or ldn < V or ldn % 8 or not 0 <= int(guide.start) < n:
+            raise ValueError(f"guide: table {tuple(t.shape)} against n_states={guide.n_states}, ldn={guide.ldn} (>= {V}, a multiple of 8), "
+                             f"start={guide.start}")
+        if int(min_new_tokens or 0) > 0:
+            raise ValueError("a guide cannot be combined with min_new_tokens > 0: an accepting state with only EOS left would have no token")
+        host = guide.host_table if guide.host_table is not None else t.cpu().numpy()
+        guided.check_no_dead_end(host[:, :V], None if sampling is None else sampling["bias"], int(guide.start))
 
     @staticmethod
     def _sampling_vectors(V: int, T: int, eos_token_ids, do_sample: bool, min_p, presence_penalty, frequency_penalty,

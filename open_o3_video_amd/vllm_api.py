@@ -26,12 +26,43 @@ from typing import Any, List, Optional, Sequence
 import numpy as np
 import torch
 
+from . import guided
 from . import vision_process as vp
 from .config import O3VConfig
 from .engine import O3VEngine
 from .weights import DeviceWeights, getter_from_safetensors_dir
 
 MAX_LOGPROBS = 20   # vLLM's default max_logprobs (the kernels' O3V_MAX_LOGPROBS)
+
+
+@dataclass
+class GuidedDecodingParams:
+    """vLLM 0.7.2's GuidedDecodingParams.  Built: `regex` and `choice` (exactly one; the subset and semantics of
+    open_o3_video_amd.guided).  `json`, `grammar` and `json_object` are refused by name; `backend` and
+    `whitespace_pattern` are accepted and ignored (there is one backend, and no JSON guide to put whitespace into)."""
+    regex: Optional[str] = None
+    choice: Optional[Sequence[str]] = None
+    json: Any = None
+    grammar: Any = None
+    json_object: Any = None
+    backend: Optional[str] = None
+    whitespace_pattern: Optional[str] = None
+
+    def __post_init__(self):
+        for name in ("json", "grammar", "json_object"):
+            if getattr(self, name) is not None:
+                raise ValueError(f"SamplingParams.guided_decoding: {name} guides are not supported (regex and choice are)")
+        if (self.regex is None) == (self.choice is None):
+            raise ValueError("SamplingParams.guided_decoding needs exactly one of regex / choice")
+        if self.regex is not None and (not isinstance(self.regex, str) or not self.regex):
+            raise ValueError("SamplingParams.guided_decoding: regex must be a non-empty string")
+        if self.choice is not None:
+            self.choice = list(self.choice) if not isinstance(self.choice, str) else self.choice
+            guided.choice_regex(self.choice)    # a non-empty list of non-empty strings
+
+    @property
+    def pattern(self) -> str:
+        return self.regex if self.regex is not None else guided.choice_regex(self.choice)
 
 
 @dataclass
@@ -58,10 +89,10 @@ class SamplingParams:
     logit_bias: Optional[dict] = None       # {token id: bias}
     allowed_token_ids: Optional[Sequence[int]] = None
     bad_words: Optional[Sequence[str]] = None
+    guided_decoding: Any = None             # GuidedDecodingParams or a dict of its keys: regex / choice
     # vLLM arguments that are not built: anything but None is refused by name
     best_of: Any = None
     logits_processors: Any = None
-    guided_decoding: Any = None
     truncate_prompt_tokens: Any = None
 
     def __post_init__(self):
@@ -69,9 +100,18 @@ class SamplingParams:
             v = getattr(self, name)
             if v is not None and not 0 <= int(v) <= MAX_LOGPROBS:
                 raise ValueError(f"Requested {name} of {v}, which is outside the allowed range 0..{MAX_LOGPROBS}")
-        for name in ("best_of", "logits_processors", "guided_decoding", "truncate_prompt_tokens"):
+        for name in ("best_of", "logits_processors", "truncate_prompt_tokens"):
             if getattr(self, name) is not None:
                 raise ValueError(f"SamplingParams.{name} is not supported")
+        if isinstance(self.guided_decoding, dict):
+            unknown = set(self.guided_decoding) - set(GuidedDecodingParams.__dataclass_fields__)
+            if unknown:
+                raise ValueError(f"SamplingParams.guided_decoding: unknown keys {sorted(unknown)}")
+            self.guided_decoding = GuidedDecodingParams(**self.guided_decoding)
+        elif self.guided_decoding is not None and not isinstance(self.guided_decoding, GuidedDecodingParams):
+            raise ValueError("SamplingParams.guided_decoding must be a GuidedDecodingParams or a dict of its keys")
+        if self.guided_decoding is not None and self.min_tokens > 0:
+            raise ValueError("SamplingParams.guided_decoding cannot be combined with min_tokens > 0")
         if isinstance(self.seed, (list, tuple)):
             raise ValueError("SamplingParams.seed: a per-request list of seeds is not supported (pass a list of SamplingParams)")
         if isinstance(self.top_k, bool) or int(self.top_k) != self.top_k or self.top_k < -1 or self.top_k == 0:
@@ -301,6 +341,10 @@ class LLM:
         # (O3VEngine.generate(shared_prefix_len=...)); counted in shared_prefix_calls / shared_prefix_rows
         self.share_video_prefix = bool(share_video_prefix)
         self.shared_prefix_calls = self.shared_prefix_rows = 0
+        # guided decoding: the token-level automata of the last two (pattern, EOS ids) on the device, and the tokenizer's byte strings
+        self._guides = {}
+        self._token_bytes = None
+        self.guide_cache_hits = 0
         # native video inputs: HF's Qwen2_5_VLProcessor gives every video second_per_grid_ts = temporal_patch_size / fps with
         # fps = 2.0 unless mm_processor_kwargs={"fps": ...} says otherwise (TF:models/qwen2_5_vl/processing_qwen2_5_vl.py:143-153;
         # the reference passes none, R:eval/models/model_vllm.py:18-26)
@@ -483,6 +527,27 @@ class LLM:
                 banned += [int(t) for t in ids if int(t) not in banned]
         return banned
 
+    GUIDE_ENTRIES = 2
+
+    def _guide(self, gd: GuidedDecodingParams, eos: Sequence[int]) -> "guided.Guide":
+        """The device table of a pattern under the call's EOS ids: compiled once per (pattern, EOS ids, tokenizer), two kept."""
+        V = self.cfg.text.vocab_size
+        key = (gd.pattern, tuple(eos), id(self.tokenizer))
+        g = self._guides.get(key)
+        if g is not None:
+            self.guide_cache_hits += 1
+            self._guides[key] = self._guides.pop(key)      # most recent last
+            return g
+        if self._token_bytes is None or self._token_bytes[0] != id(self.tokenizer):
+            self._token_bytes = (id(self.tokenizer), guided.token_bytes(self.tokenizer, V))
+        table = guided.token_table(guided.compile_regex(gd.pattern), self._token_bytes[1], eos, V)
+        g = guided.Guide(table=torch.from_numpy(table).to(self.engine.dev), n_states=table.shape[0], ldn=table.shape[1], start=0,
+                         host_table=table)
+        while len(self._guides) >= self.GUIDE_ENTRIES:
+            self._guides.pop(next(iter(self._guides)))
+        self._guides[key] = g
+        return g
+
     def generate(self, inputs, sampling_params=None, use_tqdm: bool = False):
         """`sampling_params`: one SamplingParams for every request, or a list with one per request.  Requests with equal parameters
         run together exactly as a single-parameter call runs them; results come back in input order, and request ids / default
@@ -550,6 +615,8 @@ class LLM:
                 raise ValueError("allowed_token_ids leaves no token to emit once the banned tokens"
                                  + (" and, before min_tokens, the stop ids" if left else "") + " are taken out")
             common["allowed_token_ids"] = list(sp.allowed_token_ids)
+        if sp.guided_decoding is not None:      # the same guide through every call site below (rows, shared-prefix groups, n samples)
+            common["guide"] = self._guide(sp.guided_decoding, eos)
         stop_strs = list(sp.stop)
 
         def tok_decode(toks):
