@@ -177,6 +177,27 @@ int o3v_gemv_norm_qkv_rope_fp8(const void* X, const void* norm_w, float eps, con
                                void* kcache, void* vcache, int slot, int Hq, int Hkv, int D, int Tmax, int cs_stride_row,
                                int cs_off, o3v_stream_t stream);
 
+/* Decode linears on MXFP4 weights (OCP MX v1.0; the MLP matrices of an opt-in engine).  A block is 32 consecutive k of one row of the
+ * packed matrix: one e8m0 scale byte (2^(s - 127)) and 32 e2m1 codes, two per byte, element 2i in the low nibble of byte i.
+ * W4 uint8 [N, K/2], S4 uint8 [N, K/32], K % 32 == 0.  M <= 3 rows (else O3V_ERR_ARG): out = epi(rmsnorm(X; norm_w) . mxfp4(W4, S4)[n]
+ * + bias), x and the accumulation as in the bf16 path -- the codes are widened to bf16 exactly with their block scale applied
+ * (v_cvt_scalef32_pk_bf16_fp4) and meet x in v_dot2c_f32_bf16; no per-row scale multiplies the sum.  norm_w may be NULL.
+ * Epilogues NONE / RESIDUAL / SWIGLU (W4 then holds the interleaved gate/up matrix, N % 32 == 0). */
+int o3v_linear_decode_mxfp4(const void* X, const void* norm_w, float eps, const void* W4, const void* S4, const void* bias,
+                            const void* res, void* out, int M, int N, int K, int ldx, int ldo, int ldr, int epilogue,
+                            o3v_stream_t stream);
+/* MXFP4 weights for 4 <= M <= 32 rows (else O3V_ERR_ARG) of already normalised x on the fragment-major images: W4p
+ * [N/16][K/128][64 lanes][16 B] -- lane l of (row block, 128-wide k step t) holds the MX block of row l & 15, k = 128 t + 32 (l >> 4)
+ * .. + 32 -- and S4p [N/16][ceil(K/512)][64 lanes][4 B], the same lane's scale bytes of steps 4 q .. 4 q + 3 (padding bytes past
+ * K/128 are never read).  Widened in registers as above, multiplied on the bf16 matrix cores (v_mfma_f32_16x16x32_bf16).
+ * Epilogues NONE / RESIDUAL / SWIGLU.  K % 128 == 0, N % 16 == 0 (SWIGLU: N % 32 == 0). */
+int o3v_linear_decode_mxfp4_rows(const void* X, const void* W4p, const void* S4p, const void* bias, const void* res, void* out, int M,
+                                 int N, int K, int ldx, int ldo, int ldr, int epilogue, o3v_stream_t stream);
+/* bf16 rows [rows, cols] (row pitch ld_in elements) -> MXFP4 codes uint8 [rows, cols/2] + scales uint8 [rows, cols/32], both dense.
+ * Per block: e = floor(log2(amax)) - 2 clamped to [-125, 125] (an all-zero block: e = 0), scale byte e + 127, codes = v / 2^e
+ * rounded to nearest even on {0, 0.5, 1, 1.5, 2, 3, 4, 6}, saturating at 6, bit 3 = sign.  cols % 32 == 0, ld_in % 8 == 0. */
+int o3v_quantize_rows_mxfp4(const void* x, void* codes, void* scales, int rows, int cols, int ld_in, o3v_stream_t stream);
+
 /* ---- attention ---------------------------------------------------------------------------------------------- */
 /* tiles: int32[n_tiles][8] = {q_row0, q_rows (<= rows_per_tile), k_row0, k_len, causal_off, k_lo, batch, own_lo};
  * word 7 is read by o3v_attn_tiles_prefix with a prompt entry only (see there) and is 0 everywhere else;
@@ -442,6 +463,13 @@ typedef struct {
     /* optional fragment-major fp8 images [N/16][K/64][64][16 B] of the four matrices (same scales): 4..32 decode rows stream
      * these (o3v_linear_decode_fp8_rows); q/k/v only without the fused rotation (Qwen3-VL) */
     const void *qkv_w8p, *o_w8p, *gu_w8p, *down_w8p;
+    /* optional MXFP4 images of the two MLP matrices (NULL = none; they come with the fp8 copies above, which the attention
+     * projections, the W8A8 prefill and the fall-back keep using): row-major codes [N, K/2] + scales [N, K/32] -- a decode of <= 3 rows
+     * on fp8 rows streams these for gate/up and down_proj (o3v_linear_decode_mxfp4) when both are present ... */
+    const void *gu_w4, *down_w4, *gu_s4, *down_s4;
+    /* ... and the fragment-major codes + scale images of o3v_linear_decode_mxfp4_rows: 4..32 rows on fp8 fragments stream these
+     * when both are present (a matrix whose K is no multiple of 128 has none: the call's MLP then stays on the fp8 fragments) */
+    const void *gu_w4p, *down_w4p, *gu_s4p, *down_s4p;
 } o3v_llm_layer_w;
 
 typedef struct {
@@ -679,6 +707,10 @@ typedef struct {
     int src_dtype, src_rows, src_cols;   /* a source row >= src_rows is a zero row */
     int rows, cols;        /* destination slot; cols % 16 == 0, every dst pointer 16-byte aligned */
     int blk0, nblk, blk_stride;          /* destination row blocks blk0 + i * blk_stride (16 rows each), i < nblk */
+    void* dst4;            /* optional MXFP4 codes [rows][cols/2] (o3v_quantize_rows_mxfp4's rule); cols % 32 == 0 */
+    void* dst4_scale;      /* uint8 [rows][cols/32], needed with dst4 */
+    void* dst4_frag;       /* optional fragment-major codes (needs dst4; rows % 16 == 0, cols % 128 == 0): [rows/16][cols/128][64][16] */
+    void* dst4_frag_scale; /* their scale image [rows/16][ceil(cols/512)][64][4], needed with dst4_frag; padding bytes are not written */
 } o3v_repack_desc;
 /* Rewrites the destination row blocks of d in every image d names, from one read of the source (two with fp8 images: row amax,
  * then the write pass).  Bytes equal a fresh DeviceWeights load of the same tensor; rows outside the blocks are not touched. */

@@ -31,7 +31,8 @@ class VitDesc(C.Structure):
 class LlmLayerW(C.Structure):
     _fields_ = [(n, vp) for n in ("ln1", "ln2", "qkv_w", "qkv_b", "o_w", "gu_w", "down_w", "qkv_wp", "o_wp", "gu_wp", "down_wp",
                                   "qkv_w8", "o_w8", "gu_w8", "down_w8", "qkv_s", "o_s", "gu_s", "down_s", "q_norm", "k_norm",
-                                  "qkv_w8p", "o_w8p", "gu_w8p", "down_w8p")]
+                                  "qkv_w8p", "o_w8p", "gu_w8p", "down_w8p", "gu_w4", "down_w4", "gu_s4", "down_s4", "gu_w4p", "down_w4p",
+                                  "gu_s4p", "down_s4p")]
 
 
 class Vit3BlockW(C.Structure):
@@ -96,7 +97,8 @@ class PrefillOpts(C.Structure):
 class RepackDesc(C.Structure):
     _fields_ = [(n, vp) for n in ("src", "row_map", "col_map", "dst", "dst_frag", "dst8", "dst8_scale", "dst8_frag")] + \
                [("src_ld", C.c_int64)] + [(n, i32) for n in ("src_dtype", "src_rows", "src_cols", "rows", "cols", "blk0", "nblk",
-                                                          "blk_stride")]
+                                                          "blk_stride")] + \
+               [(n, vp) for n in ("dst4", "dst4_scale", "dst4_frag", "dst4_frag_scale")]
 
 
 SRC_BF16, SRC_F32 = 0, 1   # O3V_SRC_* in include/o3v.h
@@ -159,6 +161,9 @@ SIGNATURES = {
     "o3v_linear_decode_fp8": [vp, vp, f32, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp],
     "o3v_gemv_norm_qkv_rope_fp8": [vp, vp, f32, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp],
     "o3v_linear_decode": [vp, vp, f32, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp],
+    "o3v_linear_decode_mxfp4": [vp, vp, f32, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp],
+    "o3v_linear_decode_mxfp4_rows": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp],
+    "o3v_quantize_rows_mxfp4": [vp, vp, vp, i32, i32, i32, vp],
     "o3v_linear_decode_norm_next": [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, f32, vp, i32, vp, C.c_uint32, vp],
     "o3v_gemv_norm_bf16": [vp, vp, f32, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp],
     "o3v_sample_top_p": [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, f32, f32, u64, vp, i32, i32, vp, vp],

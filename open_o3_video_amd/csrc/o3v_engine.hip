@@ -395,7 +395,8 @@ extern "C" int o3v_llm_prefill_ex(const o3v_llm_desc* d, void* x, const void* co
 }
 
 namespace {
-enum Weights { W_BF16, W_FP8_ROWS, W_FP8_FRAGS };  // what the decode linears stream: bf16, fp8 rows (<= 3 rows), fp8 fragments (4..32 rows)
+// what the decode linears stream: bf16, fp8 rows (<= 3 rows), fp8 fragments (4..32 rows); the MLP alone: MXFP4 rows / fragments
+enum Weights { W_BF16, W_FP8_ROWS, W_FP8_FRAGS, W_MXFP4_ROWS, W_MXFP4_FRAGS };
 // pre_normed: `normed` already holds RMSNorm(x; final_norm) (the last down_proj of a batched decode step normalised it, TailNorm)
 int llm_head(const o3v_llm_desc* d, const void* x, int ldx, int rows, void* normed, void* logits, Weights wf, o3v_stream_t s,
              bool pre_normed = false) {
@@ -450,7 +451,7 @@ extern "C" int o3v_llm_decode_lp(const o3v_llm_desc* d, const o3v_decode_state* 
 namespace {
 // Which kernels the steps of one decode call launch; layer 0's weights speak for the stack.  Set and explained in decide_regime().
 struct Regime {
-    Weights weights, qkv_weights;                     // of the linears; of q/k/v
+    Weights weights, qkv_weights, mlp_weights;        // of the linears; of q/k/v; of gate/up and down_proj
     bool norm_apart, qkv_fused_norm, qk_norm, group;  // fixed for the call
     bool kv8, kv8_emulate;                            // fp8 K/V cache; its arithmetic emulated on a bf16 cache (tests)
     const int* own_lo;                                // group rows with left-padded suffixes in their own caches: the gap mask, else NULL
@@ -485,6 +486,13 @@ Regime decide_regime(const o3v_llm_desc* d, const o3v_decode_state* st) {
     const bool fp8b = B >= 4 && l0.gu_w8p && l0.down_w8p && l0.o_w8p;
     r.weights = fp8 ? W_FP8_ROWS : fp8b ? W_FP8_FRAGS : W_BF16;
     r.qkv_weights = fp8b && !l0.qkv_w8p ? W_BF16 : r.weights;  // (without a fragment image of its own q/k/v stays on the bf16 weights)
+    // MXFP4 images of the MLP (opt-in, beside the fp8 copies): gate/up and down_proj stream them wherever the call runs on fp8 rows /
+    // fp8 fragments and BOTH matrices have the image of that form; nothing else of the regime changes (norms, q/k/v, o_proj, the
+    // one-launch attention block and the head are those of the fp8 call).  A matrix without the image (K no multiple of 128 for the
+    // fragments) leaves the whole MLP on r.weights.
+    r.mlp_weights = r.weights;
+    if (r.weights == W_FP8_ROWS && l0.gu_w4 && l0.down_w4 && l0.gu_s4 && l0.down_s4) r.mlp_weights = W_MXFP4_ROWS;
+    if (r.weights == W_FP8_FRAGS && l0.gu_w4p && l0.down_w4p && l0.gu_s4p && l0.down_s4p) r.mlp_weights = W_MXFP4_FRAGS;
     r.qk_norm = l0.q_norm != nullptr;  // Qwen3-VL: per-head RMSNorm between the q/k/v linear and the rotation
     r.group = st->group > 1;           // the rows of a group share the prompt K/V: read it once per group
     // batch 1: q/k/v + attention + merge + o_proj as ONE launch (o3v_fused.hip); epoch = index of the launch in this generate call
@@ -565,6 +573,13 @@ struct Decode {
         if (wf == W_FP8_FRAGS) return o3v_linear_decode_fp8_rows(X, W8p, sc, bias, res, out, B, N, K, K, ldo, res ? H : 0, epi, s);
         return o3v_linear_decode(X, ln, eps, W, Wp, bias, res, out, B, N, K, K, ldo, res ? H : 0, epi, s);
     }
+    // one MLP linear on the MXFP4 images (rows: W4 / S4 row-major, ln may be fused; fragments: X arrives normalised)
+    int lin4(Weights wf, const void* X, const void* ln, const void* W4, const void* S4, void* out, int N, int K, int ldo, int epi) {
+        const void* res = epi == O3V_EPI_RESIDUAL ? st->x : nullptr;
+        if (wf == W_MXFP4_ROWS)
+            return o3v_linear_decode_mxfp4(X, ln, ln ? d->rms_eps : 0.f, W4, S4, nullptr, res, out, B, N, K, K, ldo, res ? H : 0, epi, s);
+        return o3v_linear_decode_mxfp4_rows(X, W4, S4, nullptr, res, out, B, N, K, K, ldo, res ? H : 0, epi, s);
+    }
     // q/k/v (+norm, rope, cache append) of layer l
     int qkv(int l, const o3v_llm_layer_w& lw) {
         const Weights wf = r.qkv_weights;
@@ -618,8 +633,13 @@ struct Decode {
     int mlp(int l, const o3v_llm_layer_w& lw) {
         const bool frags = r.weights == W_FP8_FRAGS, apart = frags || r.norm_apart;
         if (apart && (frags || !h2_ready)) TRY(o3v_rmsnorm(st->x, lw.ln2, w.h, B, H, H, H, d->rms_eps, s));
-        TRY(lin(r.weights, apart ? w.h : st->x, apart ? nullptr : lw.ln2, lw.gu_w, lw.gu_wp, lw.gu_w8, lw.gu_w8p, lw.gu_s, nullptr, w.mlp, 2 * I,
-                H, I, O3V_EPI_SWIGLU));
+        const void *xin = apart ? w.h : st->x, *ln = apart ? nullptr : lw.ln2;
+        if (r.mlp_weights == W_MXFP4_ROWS)
+            TRY(lin4(W_MXFP4_ROWS, xin, ln, lw.gu_w4, lw.gu_s4, w.mlp, 2 * I, H, I, O3V_EPI_SWIGLU));
+        else if (r.mlp_weights == W_MXFP4_FRAGS)
+            TRY(lin4(W_MXFP4_FRAGS, xin, ln, lw.gu_w4p, lw.gu_s4p, w.mlp, 2 * I, H, I, O3V_EPI_SWIGLU));
+        else
+            TRY(lin(r.weights, xin, ln, lw.gu_w, lw.gu_wp, lw.gu_w8, lw.gu_w8p, lw.gu_s, nullptr, w.mlp, 2 * I, H, I, O3V_EPI_SWIGLU));
         return down_proj(l, lw);
     }
     int down_proj(int l, const o3v_llm_layer_w& lw) {  // also behind the layer block
@@ -632,6 +652,8 @@ struct Decode {
             (last ? normed_ready : h_ready) = true;
             return O3V_OK;
         }
+        if (r.mlp_weights == W_MXFP4_ROWS) return lin4(W_MXFP4_ROWS, w.mlp, nullptr, lw.down_w4, lw.down_s4, st->x, H, I, H, O3V_EPI_RESIDUAL);
+        if (r.mlp_weights == W_MXFP4_FRAGS) return lin4(W_MXFP4_FRAGS, w.mlp, nullptr, lw.down_w4p, lw.down_s4p, st->x, H, I, H, O3V_EPI_RESIDUAL);
         return lin(r.weights, w.mlp, nullptr, lw.down_w, lw.down_wp, lw.down_w8, lw.down_w8p, lw.down_s, nullptr, st->x, H, I, H,
                    O3V_EPI_RESIDUAL);
     }

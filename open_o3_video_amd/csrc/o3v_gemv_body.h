@@ -3,6 +3,7 @@
 #pragma once
 #include "o3v_common.h"
 #include "o3v_handoff.h"
+#include "o3v_mxfp4.h"
 
 #define EPI_NONE 0
 #define EPI_RESIDUAL 1
@@ -56,6 +57,34 @@ __device__ __forceinline__ void fma16_fp8(const u32x4& w, const u32x4& xa, const
 #undef O3V_F8
 }
 
+// 32 MXFP4 (e2m1) weights of one block x 32 bf16 of x -> fp32 accumulate: v_cvt_scalef32_pk_bf16_fp4 widens one code byte to two
+// bf16 with the block scale 2^e applied -- EXACTLY: an e2m1 value has one mantissa bit and 2^e * it is a normal bf16 -- then the
+// same v_dot2c_f32_bf16 as the bf16 path.  The 16 widened pairs are shared by the rows of x: 16 cvt + 16 M dot2 per 16 weight bytes.
+__device__ __forceinline__ void widen32_fp4(const u32x4& w, float sc, bf16x2_t (&o)[16]) {
+    const uint32_t w0 = w[0], w1 = w[1], w2 = w[2], w3 = w[3];
+#define O3V_F4(J, WW)                                                      \
+    o[4 * J + 0] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(WW, sc, 0);   \
+    o[4 * J + 1] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(WW, sc, 1);   \
+    o[4 * J + 2] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(WW, sc, 2);   \
+    o[4 * J + 3] = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(WW, sc, 3);
+    O3V_F4(0, w0)
+    O3V_F4(1, w1)
+    O3V_F4(2, w2)
+    O3V_F4(3, w3)
+#undef O3V_F4
+}
+// pair p = 4 j + b (byte b of weight dword j: k = 8 j + 2 b, + 1) meets dword p & 3 of x chunk p >> 2
+__device__ __forceinline__ void fma32_fp4(const bf16x2_t (&wd)[16], const u32x4 (&x)[4], float& acc) {
+#pragma unroll
+    for (int h = 0; h < 4; ++h) {
+        const uint32_t x0 = x[h][0], x1 = x[h][1], x2 = x[h][2], x3 = x[h][3];
+        acc = __builtin_amdgcn_fdot2_f32_bf16(wd[4 * h + 0], __builtin_bit_cast(bf16x2_t, x0), acc, false);
+        acc = __builtin_amdgcn_fdot2_f32_bf16(wd[4 * h + 1], __builtin_bit_cast(bf16x2_t, x1), acc, false);
+        acc = __builtin_amdgcn_fdot2_f32_bf16(wd[4 * h + 2], __builtin_bit_cast(bf16x2_t, x2), acc, false);
+        acc = __builtin_amdgcn_fdot2_f32_bf16(wd[4 * h + 3], __builtin_bit_cast(bf16x2_t, x3), acc, false);
+    }
+}
+
 struct RopeArgs {  // EPI_QKVROPE destinations (one token per row m, cache slot `slot`, table row m*cs_stride+cs_off)
     const bf16_t *cosT, *sinT;
     bf16_t *qout, *kc, *vc;
@@ -84,20 +113,26 @@ __device__ __forceinline__ void gemv_store_bf16(bf16_t* p, bf16_t v) {
 // WB = bytes per weight element: 2 = bf16 rows; 1 = fp8 (OCP e4m3fn) rows with one fp32 dequantisation scale per output row
 // (`wscale`): a 16-byte weight chunk then spans 16 k (two 16-byte chunks of x) and the row's sum is multiplied by its scale
 // before the bias.  K % 16 == 0 for WB == 1.
+// WB = 0: MXFP4 rows (o3v_mxfp4.h) -- half a byte per element, `wscale4` = one e8m0 byte per 32 k [N][K/32].  A 16-byte weight chunk
+// is one MX block: 32 k, four 16-byte chunks of x, its scale applied at the widening (no per-row scale).  The k per lane and step
+// stays 32: a trip keeps fewer steps in flight (U = 2 at one row of x, 1 above) and the launcher gives a wave more rows instead.
+// K % 32 == 0.
 template <int M, int R, int KS, int EPI, bool NORM, bool PUB = false, int UU = 0, int NW = 4, int WB = 2>
 __device__ __forceinline__ void gemv_body(const bf16_t* __restrict__ X, const bf16_t* __restrict__ W,
                                           const bf16_t* __restrict__ bias, const bf16_t* __restrict__ res,
                                           bf16_t* __restrict__ out, const bf16_t* __restrict__ norm_w, float eps, int N,
                                           int K, int ldx, int ldw, int ldo, int ldr, const RopeArgs& ra, const int bid,
-                                          char* smem, const float* __restrict__ wscale = nullptr) {
+                                          char* smem, const float* __restrict__ wscale = nullptr,
+                                          const uint8_t* __restrict__ wscale4 = nullptr) {
     static_assert(NW % KS == 0, "K slices must divide the waves of a workgroup");
-    static_assert(WB == 1 || WB == 2, "bf16 or fp8 weights");
+    static_assert(WB == 0 || WB == 1 || WB == 2, "bf16, fp8 or MXFP4 weights");
+    constexpr bool W4 = WB == 0;
     constexpr int RG = NW / KS;                                  // row groups per block
     constexpr int NT = NW * 64;                                  // threads per block
-    constexpr int XPC = 2 / WB;                                  // 16-byte chunks of x per 16-byte chunk of weights
+    constexpr int XPC = W4 ? 4 : (WB == 1 ? 2 : 1);              // 16-byte chunks of x per 16-byte chunk of weights
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int rg = wave / KS, ks = wave % KS;
-    const int nch = K >> (WB == 1 ? 4 : 3);                      // weight chunks per row
+    const int nch = K >> (W4 ? 5 : WB == 1 ? 4 : 3);             // weight chunks per row
     const int nxc = K >> 3;                                      // x chunks per row
 
     // ---- rows of this wave.  SWIGLU: R/2 output columns = R/2 (gate,up) row pairs of the 16-row-interleaved weight
@@ -124,8 +159,11 @@ __device__ __forceinline__ void gemv_body(const bf16_t* __restrict__ X, const bf
 #pragma unroll
     for (int r = 0; r < R; ++r) {
         const int rr = rows[r] < N ? rows[r] : N - 1;  // tail rows re-read a valid row, never stored
-        wp[r] = reinterpret_cast<const u32x4*>(reinterpret_cast<const char*>(W) + (size_t)rr * ldw * WB);
+        wp[r] = reinterpret_cast<const u32x4*>(reinterpret_cast<const char*>(W) + (W4 ? (size_t)rr * ldw / 2 : (size_t)rr * ldw * WB));
     }
+    const uint8_t* sp[R];  // MXFP4: the row's scale bytes, one per weight chunk
+#pragma unroll
+    for (int r = 0; r < R; ++r) sp[r] = W4 ? wscale4 + (size_t)(rows[r] < N ? rows[r] : N - 1) * nch : nullptr;
     // Epilogue operands (bias, residual, rotary cos/sin) are requested here, a whole kernel ahead of their use: these
     // kernels live for 7-25 us, and a dependent L2 round trip at the tail is 5-10 % of that.
     float e_scale[R];
@@ -157,10 +195,11 @@ __device__ __forceinline__ void gemv_body(const bf16_t* __restrict__ X, const bf
     const int c_begin = ks * sps * 64;
     int c_end = c_begin + sps * 64;
     c_end = c_end < nch ? c_end : nch;
-    constexpr int U = UU > 0 ? UU : ((R >= 4) ? 2 : 4);
+    constexpr int U = UU > 0 ? UU : W4 ? (M == 1 ? 2 : 1) : ((R >= 4) ? 2 : 4);
 
     // weight loads of one trip (U steps x R rows, 16 B per lane each): issued as early as possible
     u32x4 wv[U][R];
+    uint32_t sv[W4 ? U : 1][W4 ? R : 1];  // MXFP4: the scale byte of each chunk
     u32x4 xg[NORM ? 1 : U][NORM ? 1 : M][XPC];  // un-normalised x comes from global memory (L2): fetched one trip ahead, with the weights
     auto load_x = [&](int c0) {
 #pragma unroll
@@ -185,6 +224,7 @@ __device__ __forceinline__ void gemv_body(const bf16_t* __restrict__ X, const bf
             for (int r = 0; r < R; ++r) {
                 wv[u][r] = __builtin_nontemporal_load(wp[r] + cc);
                 if (!in) wv[u][r] = (u32x4){0, 0, 0, 0};
+                if constexpr (W4) sv[u][r] = sp[r][cc];  // (an out-of-range lane: a valid scale on zero codes)
             }
         }
         if (!NORM) load_x(c0);
@@ -327,14 +367,22 @@ __device__ __forceinline__ void gemv_body(const bf16_t* __restrict__ X, const bf
 #pragma unroll
         for (int u = 0; u < U; ++u)
 #pragma unroll
-            for (int r = 0; r < R; ++r)
+            for (int r = 0; r < R; ++r) {
+                if constexpr (W4) {
+                    bf16x2_t wd[16];
+                    widen32_fp4(wv[u][r], mx4_scale(sv[u][r]), wd);
 #pragma unroll
-                for (int m = 0; m < M; ++m) {
-                    if constexpr (WB == 1)
-                        fma16_fp8(wv[u][r], xv[u][m][0], xv[u][m][XPC - 1], acc[r][m]);
-                    else
-                        fma8(wv[u][r], xv[u][m][0], acc[r][m]);
+                    for (int m = 0; m < M; ++m) fma32_fp4(wd, xv[u][m], acc[r][m]);
+                } else {
+#pragma unroll
+                    for (int m = 0; m < M; ++m) {
+                        if constexpr (WB == 1)
+                            fma16_fp8(wv[u][r], xv[u][m][0], xv[u][m][XPC - 1], acc[r][m]);
+                        else
+                            fma8(wv[u][r], xv[u][m][0], acc[r][m]);
+                    }
                 }
+            }
         if (c0 + 64 * U < c_end) load_w(c0 + 64 * U);
     }
 #pragma unroll

@@ -6,18 +6,23 @@
 //   bf16 fragment-major [rows/16][cols/32][64 lanes][8]   (weights.pack_mfma_fragments)
 //   fp8 e4m3fn codes    [rows][cols] + one power-of-two f32 scale per row (weights.quantize_rows_fp8, o3v_fp8_rows.h)
 //   fp8 fragment-major  [rows/16][cols/64][64 lanes][16]  (weights.pack_mfma_fragments_fp8)
+//   MXFP4 codes         [rows][cols/2] + one e8m0 scale byte per 32 columns [rows][cols/32] (weights.quantize_rows_mxfp4, o3v_mxfp4.h)
+//   MXFP4 fragment-major [rows/16][cols/128][64 lanes][16] + its scale image [rows/16][ceil(cols/512)][64 lanes][4]
+//                       (weights.pack_mfma_fragments_mxfp4)
 //
 // The source is bf16 (copied bit for bit) or fp32 (rounded to nearest even with torch's rule: any NaN -> 0x7FC0), so the bytes
 // equal what a fresh DeviceWeights load of the same tensor builds.  One workgroup (4 waves) per 16-row block; wave w takes the
 // 64-column groups w, w+4, ...; lane l of a wave takes row l & 15, columns 64t + 16 (l >> 4) .. +16.  Then the fp8 fragment store
 // of a wave is one contiguous KiB, its bf16 fragment stores cover two contiguous KiB, and its row-major stores 16 rows x 128 B.
 // With fp8 images the block is read twice: a row-amax pass, then the pass that writes (the second read comes from L2 / MALL).
+// An MX block is the 32 columns of two neighbouring lanes (l, l ^ 16): they exchange their maxima and each writes its 8 code bytes.
 // Rows outside the launched blocks are not touched in any image.
 #include <hip/hip_runtime.h>
 
 #include "../../include/o3v.h"
 #include "o3v_common.h"
 #include "o3v_fp8_rows.h"
+#include "o3v_mxfp4.h"
 
 namespace {
 
@@ -87,7 +92,12 @@ __device__ __forceinline__ void st16(void* dst, uint32_t a, uint32_t b, uint32_t
     __builtin_nontemporal_store(v, static_cast<u32x4*>(dst));   // written once, never read by this launch
 }
 
-template <bool F32, bool FP8>
+__device__ __forceinline__ void st8(void* dst, uint32_t a, uint32_t b) {
+    u32x2 v = {a, b};
+    __builtin_nontemporal_store(v, static_cast<u32x2*>(dst));
+}
+
+template <bool F32, bool FP8, bool FP4>
 __global__ __launch_bounds__(256) void repack_rows_kernel(const o3v_repack_desc d, const int vec) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int r = lane & 15, sub = lane >> 4;
@@ -158,6 +168,29 @@ __global__ __launch_bounds__(256) void repack_rows_kernel(const o3v_repack_desc 
             st16(q8 + (size_t)row * d.cols + c0, a.x, a.y, b.x, b.y);
             if (q8f) st16(q8f + blk_base + ((size_t)t * 64 + lane) * 16, a.x, a.y, b.x, b.y);   // 64-wide step t, lane r + 16 sub
         }
+        if constexpr (FP4) {
+            // MX block b32 = 2 t + (sub >> 1) of the row: this lane's 16 columns are its half (sub & 1)
+            uint32_t amax = 0u;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const uint32_t a = mx4_amax2(p[j]);
+                amax = a > amax ? a : amax;
+            }
+            const uint32_t other = (uint32_t)__shfl_xor((int)amax, 16, 64);
+            amax = other > amax ? other : amax;
+            const uint32_t code = mx4_scale_code(amax);
+            const float inv4 = mx4_inv_scale(code);
+            const uint32_t lo = mx4_codes4(p[0], p[1], inv4) | (mx4_codes4(p[2], p[3], inv4) << 16);
+            const uint32_t hi = mx4_codes4(p[4], p[5], inv4) | (mx4_codes4(p[6], p[7], inv4) << 16);
+            const int b32 = 2 * t + (sub >> 1), half = sub & 1, nb32 = d.cols >> 5;
+            st8(static_cast<uint8_t*>(d.dst4) + ((size_t)row * nb32 + b32) * 16 + half * 8, lo, hi);
+            if (!half) static_cast<uint8_t*>(d.dst4_scale)[(size_t)row * nb32 + b32] = (uint8_t)code;
+            if (d.dst4_frag) {   // 128-wide step b32 / 4, fragment lane r + 16 (b32 % 4)
+                const int st = b32 >> 2, fl = r + 16 * (b32 & 3), nt = d.cols >> 7, nt4 = (nt + 3) >> 2;
+                st8(static_cast<uint8_t*>(d.dst4_frag) + (((size_t)blk * nt + st) * 64 + fl) * 16 + half * 8, lo, hi);
+                if (!half) static_cast<uint8_t*>(d.dst4_frag_scale)[(((size_t)blk * nt4 + (st >> 2)) * 64 + fl) * 4 + (st & 3)] = (uint8_t)code;
+            }
+        }
     }
 }
 
@@ -175,18 +208,30 @@ extern "C" int o3v_repack_rows(const o3v_repack_desc* d, hipStream_t stream) {
     auto mis16 = [](const void* p) { return ((uintptr_t)p & 15) != 0; };
     if (mis16(d->dst) || mis16(d->dst_frag) || mis16(d->dst8) || mis16(d->dst8_frag)) return O3V_ERR_ARG;
     if (d->cols & 15) return O3V_ERR_SHAPE;
+    if (d->dst4 && !d->dst4_scale) return O3V_ERR_ARG;
+    if (d->dst4_frag && (!d->dst4 || !d->dst4_frag_scale)) return O3V_ERR_ARG;
+    if (mis16(d->dst4) || mis16(d->dst4_frag) || ((uintptr_t)d->dst4_frag_scale & 3)) return O3V_ERR_ARG;
+    if (d->dst4 && (d->cols & 31)) return O3V_ERR_SHAPE;
+    if (d->dst4_frag && ((d->rows & 15) || (d->cols & 127))) return O3V_ERR_SHAPE;
     if (d->dst_frag && ((d->rows & 15) || (d->cols & 31))) return O3V_ERR_SHAPE;
     if (d->dst8_frag && ((d->rows & 15) || (d->cols & 63))) return O3V_ERR_SHAPE;
     const int esize = d->src_dtype == O3V_SRC_F32 ? 4 : 2;
     const uintptr_t pitch = (uintptr_t)d->src | (uintptr_t)(d->src_ld * esize);   // alignment every source row start shares
     const int vec = (pitch & 15) == 0 ? 16 : (pitch & 7) == 0 ? 8 : 0;
     const dim3 grid(d->nblk), block(256);
-#define O3V_RP(F, Q) O3V_KLAUNCH((repack_rows_kernel<F, Q>), grid, block, 0, stream, *d, vec)
-    if (d->src_dtype == O3V_SRC_F32) {
-        if (d->dst8) O3V_RP(true, true); else O3V_RP(true, false);
-    } else {
-        if (d->dst8) O3V_RP(false, true); else O3V_RP(false, false);
-    }
+#define O3V_RP(F, Q, Q4) O3V_KLAUNCH((repack_rows_kernel<F, Q, Q4>), grid, block, 0, stream, *d, vec)
+#define O3V_RPQ(F)                                \
+    do {                                          \
+        if (d->dst8 && d->dst4) O3V_RP(F, true, true);   \
+        else if (d->dst8) O3V_RP(F, true, false);  \
+        else if (d->dst4) O3V_RP(F, false, true);  \
+        else O3V_RP(F, false, false);              \
+    } while (0)
+    if (d->src_dtype == O3V_SRC_F32)
+        O3V_RPQ(true);
+    else
+        O3V_RPQ(false);
+#undef O3V_RPQ
 #undef O3V_RP
     O3V_CHECK_LAUNCH();
     return O3V_OK;

@@ -128,6 +128,19 @@ def kv_cache_in_effect(kv_cache_dtype: str, head_dim: int, plan: DecodePlan) -> 
     return "fp8" if kv_cache_dtype == "fp8" and head_dim == 128 and not plan.shared_prompt else "bf16"
 
 
+def mlp_weights_in_effect(images, plan: DecodePlan) -> str:
+    """The weight format gate/up and down_proj of a generate call stream -- decide_regime's rule (csrc/o3v_engine.hip) restated on
+    the keys of DeviceWeights.t (`images`): "mxfp4" where the call decodes on fp8 rows (<= 3 independent rows) or fp8 fragments
+    (4..32 rows) and BOTH MLP matrices keep the MXFP4 image of that form, "fp8" on those rows / fragments otherwise, else "bf16"."""
+    def has(*sfx):
+        return all(f"l0.{m}{x}" in images for m in ("gu_w", "down_w") for x in sfx)
+    if plan.B <= 3 and plan.group <= 1 and has("8") and all(f"l0.{m}8" in images for m in ("qkv_w", "o_w")):
+        return "mxfp4" if has("4", "4s") else "fp8"
+    if plan.B >= 4 and has("8p") and "l0.o_w8p" in images:
+        return "mxfp4" if has("4p", "4ps") else "fp8"
+    return "bf16"
+
+
 def trimmed_length(gen: np.ndarray, eos_ids, ended: dict, done: int) -> int:
     """Columns of gen i64 [B, done] that HF would have produced: up to and including the step at which the last row finished.
     A row finishes at its first id of `eos_ids`, a row the stop checker ended (`ended`: row -> tokens it keeps) at the column the
@@ -774,6 +787,7 @@ class O3VEngine:
         buf = _DecodeBuffers(self, plan, state["S"], T, state["G"], ids_rep, state["pad_rep"], eos_token_ids, row_ids, return_margins,
                              n_lp, sampling, knobs, cosd, sind, logits, kc, vc, kc0, vc0, kv8, emulate, own=state["own"], guide=guide)
         tm["kv_cache_dtype"] = kv_dtype
+        tm["mlp_weights"] = mlp_weights_in_effect(self.w.t, plan)
         tm["kv_cache_bytes"] = int((kc.numel() + vc.numel() + (kc0.numel() + vc0.numel() if plan.shared_prompt else 0)) * 2 +
                                    sum(t.numel() * t.element_size() for t in kv8 or ()))
         use_eos = len(eos_token_ids) > 0

@@ -264,6 +264,13 @@ def shared_prefix_groups(ids_list, vkeys, visual_ids):
     return groups, sorted(rest)
 
 
+def decode_quantization(quantization: Optional[str]) -> dict:
+    """vLLM's `quantization` keyword -> the DeviceWeights switches it stands for; any value that is not built is refused by name."""
+    if quantization not in (None, "fp8", "mxfp4"):
+        raise ValueError(f"quantization={quantization!r}: only None, 'fp8' (decode rows) or 'mxfp4' (MLP decode rows) is built")
+    return dict(fp8_decode=quantization in ("fp8", "mxfp4"), mxfp4_decode=quantization == "mxfp4")
+
+
 class LLM:
     IMAGE_PAD = "<|image_pad|>"
     VIDEO_PAD = "<|video_pad|>"
@@ -292,13 +299,14 @@ class LLM:
             cfg = O3VConfig.from_pretrained(model)
             # vLLM's keyword: quantization="fp8" quantises the bf16 checkpoint's linears on load (here: fp8 e4m3fn decode rows with
             # one power-of-two scale per output row beside the bf16 matrices, which prefill keeps using; BASELINE config #5)
-            if quantization not in (None, "fp8"):
-                raise ValueError(f"quantization={quantization!r}: only None or 'fp8' (decode rows) is built")
-            engine = O3VEngine(cfg, DeviceWeights(cfg, getter_from_safetensors_dir(model), device, fp8_decode=quantization == "fp8"))
+            # "mxfp4": those fp8 rows, and MXFP4 images (OCP MX: e2m1 codes, one e8m0 scale per 32 weights, rounded to nearest on
+            # load) of the MLP matrices, which the decode streams instead -- no calibrated checkpoint behind it: parity unpinned
+            wq = decode_quantization(quantization)
+            engine = O3VEngine(cfg, DeviceWeights(cfg, getter_from_safetensors_dir(model), device, **wq))
             # vLLM's fp8 linears quantise the activations per token as well (W8A8); here that is opt-in for the compute-bound
             # prefill (fp8 x fp8 on the matrix cores), while the decode keeps bf16 activations on the exactly widened fp8 rows
-            if fp8_prefill and quantization != "fp8":
-                raise ValueError("fp8_prefill=True needs quantization='fp8'")
+            if fp8_prefill and not wq["fp8_decode"]:
+                raise ValueError("fp8_prefill=True needs quantization='fp8' or 'mxfp4'")
             engine.fp8_prefill = bool(fp8_prefill)
             tokenizer = tokenizer or _load_tokenizer(model)
             pp = os.path.join(model, "preprocessor_config.json")

@@ -77,6 +77,62 @@ def dequantize_rows_fp8(q8: torch.Tensor, s: torch.Tensor) -> torch.Tensor:
     return q8.view(torch.float8_e4m3fn).float() * s[:, None].float()
 
 
+MXFP4_GRID = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)   # OCP e2m1 magnitudes of codes 0..7; bit 3 of a code is the sign
+
+
+def quantize_rows_mxfp4(w: torch.Tensor):
+    """[N, K] bf16 -> (uint8 [N, K/2] codes, uint8 [N, K/32] scales): OCP MX v1.0 MXFP4 over blocks of 32 consecutive k of a row.
+    Per block e = floor(log2(amax)) - 2 clamped to [-125, 125] (an all-zero block: e = 0), scale byte e + 127; elements are v / 2^e
+    rounded to nearest even on the e2m1 grid {0, 0.5, 1, 1.5, 2, 3, 4, 6}, saturating at +-6 (amax / 2^e lies in [4, 8): a value
+    in (6, 8) * 2^e becomes 6 * 2^e); element 2i is the low nibble of byte i, bit 3 of a code the sign.  The clamp keeps every
+    dequantised value a normal, finite bf16, and e2m1 * 2^e is exact in bf16, so the MXFP4 path can be checked against the bf16
+    path on the very same weight values.
+    Written on bit patterns and exact products so that the device quantiser (csrc/o3v_mxfp4.h) agrees bit for bit: amax is the
+    largest magnitude PATTERN of the block, its exponent field gives e, |v| * 2^-e is exact.  Requires K % 32 == 0."""
+    N, K = w.shape
+    assert K % 32 == 0
+    bits = w.to(torch.bfloat16).contiguous().view(torch.int16).to(torch.int32).view(N, K // 32, 32) & 0xFFFF
+    mag = bits & 0x7FFF
+    amax = mag.amax(dim=2)
+    e = torch.clamp((amax >> 7) - 129, -125, 125)          # exponent field - 127 = floor(log2) of a normal; subnormals hit the clamp
+    e = torch.where(amax > 0, e, torch.zeros_like(e))
+    inv = ((127 - e) << 23).to(torch.int32).view(torch.float32)       # 2^-e
+    a = (mag << 16).to(torch.int32).view(torch.float32) * inv[:, :, None]
+    # thresholds = midpoints of the grid; a tie goes to the code with an even mantissa bit (0, 1, 2, 4)
+    code = ((a > 0.25).to(torch.int32) + (a >= 0.75) + (a > 1.25) + (a >= 1.75) + (a > 2.5) + (a >= 3.5) + (a > 5.0)) | ((bits >> 12) & 8)
+    code = code.view(N, K // 2, 2)
+    codes = (code[..., 0] | (code[..., 1] << 4)).to(torch.uint8)
+    return codes.contiguous(), (e + 127).to(torch.uint8).contiguous()
+
+
+def dequantize_rows_mxfp4(codes: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
+    """(uint8 [N, K/2], uint8 [N, K/32]) -> f32 [N, K]: e2m1(code) * 2^(scale - 127), what the kernels multiply (exact in bf16)."""
+    N = codes.shape[0]
+    c = torch.stack([codes & 15, codes >> 4], dim=-1).view(N, -1).long()
+    grid = torch.tensor(MXFP4_GRID + tuple(-v for v in MXFP4_GRID), dtype=torch.float32, device=codes.device)
+    s = (scales.to(torch.int32) << 23).view(torch.float32)
+    return (grid[c].view(N, -1, 32) * s[:, :, None]).view(N, -1)
+
+
+def pack_mfma_fragments_mxfp4(codes: torch.Tensor, scales: torch.Tensor):
+    """Row-major MXFP4 (codes uint8 [N, K/2], scales uint8 [N, K/32]) -> the fragment-major pair of
+    csrc/o3v_mxfp4.hip gemv_mfma_mxfp4_kernel, laid out like pack_mfma_fragments_fp8:
+      codes  [N/16][K/128][64 lanes][16 B]: lane l of (row block nb, 128-wide k step t) holds the MX block of row nb*16 + (l & 15),
+             k = 128 t + 32 (l >> 4) .. + 32 -- a lane's 16-byte load is one block, a wave-instruction reads one contiguous KiB;
+      scales [N/16][ceil(K/512)][64 lanes][4 B]: the same (row block, k step, lane) order with four consecutive k steps of a lane in
+             one dword (bytes of steps past K/128 are padding: 127).
+    Requires N % 16 == 0 and K % 128 == 0."""
+    N, K = codes.shape[0], codes.shape[1] * 2
+    assert N % 16 == 0 and K % 128 == 0 and scales.shape == (N, K // 32)
+    nt = K // 128
+    nt4 = (nt + 3) // 4
+    cp = codes.view(N // 16, 16, nt, 4, 16).permute(0, 2, 3, 1, 4).contiguous().view(N, K // 2)
+    sp = torch.full((N, nt4 * 16), 127, dtype=torch.uint8, device=scales.device)
+    sp[:, : nt * 4] = scales
+    sp = sp.view(N // 16, 16, nt4, 4, 4).permute(0, 2, 4, 1, 3).contiguous().view(N // 16, nt4 * 256)   # [nb][q][g][row][step in q]
+    return cp, sp
+
+
 def pad_cols(w: torch.Tensor, kpad: int) -> torch.Tensor:
     if w.shape[1] == kpad:
         return w.contiguous()
@@ -88,9 +144,11 @@ def pad_cols(w: torch.Tensor, kpad: int) -> torch.Tensor:
 class _RepackWrite:
     """One o3v_repack_rows launch: 16-row blocks row0 + i * stride (i < nblk) of slot `slot` and of its derived images."""
 
-    def __init__(self, slot, row0, nblk, stride, row_map=None, col_map=None, frag=None, q8=None, q8s=None, q8frag=None):
+    def __init__(self, slot, row0, nblk, stride, row_map=None, col_map=None, frag=None, q8=None, q8s=None, q8frag=None, q4=None,
+                 q4s=None, q4frag=None, q4frags=None):
         self.slot, self.row0, self.nblk, self.stride, self.row_map, self.col_map = slot, row0, nblk, stride, row_map, col_map
         self.frag, self.q8, self.q8s, self.q8frag = frag, q8, q8s, q8frag
+        self.q4, self.q4s, self.q4frag, self.q4frags = q4, q4s, q4frag, q4frags      # MXFP4 codes / scales, row-major and fragment-major
 
     def apply(self, t: Dict[str, torch.Tensor], src: torch.Tensor, stream):
         if src.stride(-1) != 1 or src.data_ptr() % 16:
@@ -105,14 +163,16 @@ class _RepackWrite:
                             dst_frag=ptr(self.frag), dst8=ptr(self.q8), dst8_scale=ptr(self.q8s), dst8_frag=ptr(self.q8frag),
                             src_ld=src.stride(0), src_dtype=_lib.SRC_F32 if src.dtype == torch.float32 else _lib.SRC_BF16,
                             src_rows=src.shape[0], src_cols=src.shape[1], rows=dst.shape[0], cols=dst.shape[1], blk0=self.row0,
-                            nblk=self.nblk, blk_stride=self.stride)
+                            nblk=self.nblk, blk_stride=self.stride, dst4=ptr(self.q4), dst4_scale=ptr(self.q4s),
+                            dst4_frag=ptr(self.q4frag), dst4_frag_scale=ptr(self.q4frags))
         _lib.call("o3v_repack_rows", C.byref(d), C.c_void_p(stream.cuda_stream))
 
     def bytes_written(self, t) -> int:
         rows = min(16 * self.nblk, t[self.slot].shape[0] - 16 * self.row0) if self.stride == 1 else 16 * self.nblk
         cols = t[self.slot].shape[1]
         n = rows * cols * (2 * (1 + (self.frag is not None)) + (self.q8 is not None) + (self.q8frag is not None))
-        return n + (4 * rows if self.q8s else 0)
+        n += 4 * rows if self.q8s else 0
+        return n + rows * cols // 32 * (17 * (self.q4 is not None) + 17 * (self.q4frag is not None))   # 16 code bytes + 1 scale byte per block
 
 
 class _VectorWrite:
@@ -164,11 +224,15 @@ class DeviceWeights:
     """Owns the packed tensors and the ctypes descriptors that point at them."""
 
     def __init__(self, cfg: O3VConfig, get: Callable[[str], torch.Tensor], device="cuda", batched_decode: bool = True,
-                 fp8_decode: bool = False):
+                 fp8_decode: bool = False, mxfp4_decode: bool = False):
         """batched_decode: also keep MFMA-fragment-major copies of the LLM matrices (+1x their size in HBM) so that
         decoding 2..8 sequences together (group rollout) streams weights at the same rate as batch 1.
         fp8_decode: also keep fp8 (OCP e4m3fn) copies of the LLM matrices and the head with one fp32 scale per output row
-        (quantize_rows_fp8); decode at batch <= 3 then streams those -- half the bytes per step (BASELINE config #5)."""
+        (quantize_rows_fp8); decode at batch <= 3 then streams those -- half the bytes per step (BASELINE config #5).
+        mxfp4_decode: implies fp8_decode, and also keeps MXFP4 images (quantize_rows_mxfp4: e2m1 codes, one e8m0 scale per 32 k) of
+        the two MLP matrices of every layer -- 85 % of a layer's bytes.  A decode on the fp8 rows then streams gate/up and down_proj
+        from those; attention projections and head stay on the fp8 rows, prefill and log-prob passes never use MXFP4."""
+        fp8_decode = bool(fp8_decode or mxfp4_decode)
         self.cfg = cfg
         self.device = torch.device(device)
         g = _Getter(get, self.device)
@@ -224,6 +288,19 @@ class DeviceWeights:
                     if batched_decode and q8.shape[0] % 16 == 0 and q8.shape[1] % 64 == 0:
                         keep[f"l{i}.{f}8p"] = pack_mfma_fragments_fp8(q8)       # 4..32 decode rows (config #5's N = 16 chains)
                         setattr(self.llm_layers[i], f[:-1] + "w8p", keep[f"l{i}.{f}8p"].data_ptr())
+            if mxfp4_decode:
+                for f in ("gu_w", "down_w"):
+                    w, n = keep[f"l{i}.{f}"], f[:-2]
+                    if w.shape[1] % 32:
+                        continue
+                    q4, s4 = quantize_rows_mxfp4(w)
+                    keep[f"l{i}.{f}4"], keep[f"l{i}.{f}4s"] = q4, s4
+                    setattr(self.llm_layers[i], n + "_w4", q4.data_ptr())
+                    setattr(self.llm_layers[i], n + "_s4", s4.data_ptr())
+                    if batched_decode and w.shape[0] % 16 == 0 and w.shape[1] % 128 == 0:
+                        keep[f"l{i}.{f}4p"], keep[f"l{i}.{f}4ps"] = pack_mfma_fragments_mxfp4(q4, s4)
+                        setattr(self.llm_layers[i], n + "_w4p", keep[f"l{i}.{f}4p"].data_ptr())
+                        setattr(self.llm_layers[i], n + "_s4p", keep[f"l{i}.{f}4ps"].data_ptr())
         keep["l.norm"] = l("norm.weight").contiguous()
         if tc.tie_word_embeddings:
             keep["l.head"] = keep["l.embed"]
@@ -242,6 +319,7 @@ class DeviceWeights:
                                 layer=self.llm_layers, final_norm=keep["l.norm"].data_ptr(),
                                 lm_head=keep["l.head"].data_ptr(), lm_head_p=head_p)
         self.fp8_decode = bool(fp8_decode)
+        self.mxfp4_decode = bool(mxfp4_decode)
         if fp8_decode:
             keep["l.head8"], keep["l.head8s"] = quantize_rows_fp8(keep["l.head"])
             self.llm.lm_head8, self.llm.lm_head_s = keep["l.head8"].data_ptr(), keep["l.head8s"].data_ptr()
@@ -373,8 +451,9 @@ class DeviceWeights:
         self.update_plan, self._update_alias = plan, {}
 
         def images(slot):
-            return dict(frag=slot + "p" if slot + "p" in keep else None, q8=slot + "8" if slot + "8" in keep else None,
-                        q8s=slot + "8s" if slot + "8s" in keep else None, q8frag=slot + "8p" if slot + "8p" in keep else None)
+            return {arg: slot + sfx if slot + sfx in keep else None
+                    for arg, sfx in (("frag", "p"), ("q8", "8"), ("q8s", "8s"), ("q8frag", "8p"), ("q4", "4"), ("q4s", "4s"),
+                                     ("q4frag", "4p"), ("q4frags", "4ps"))}
 
         def mat(name, shape, slot, row0=0, stride=1, nblk=None, row_map=None, col_map=None, derived=None, llm=False, why=None):
             # a layout the kernel cannot rewrite is recorded as unsupported (load_weights refuses it); loading never fails here
@@ -511,7 +590,7 @@ class DeviceWeights:
 
     def load_weights(self, named_tensors) -> set:
         """Rewrite the packed images in place from (HF name, tensor) pairs -- vLLM's model.load_weights.  Every image a slot keeps
-        (bf16 rows, fragment-major, fp8 codes + scales, fp8 fragment-major) gets the bytes a fresh DeviceWeights load of the same
+        (bf16 rows, fragment-major, fp8 codes + scales, fp8 fragment-major, MXFP4 codes + scales in both layouts) gets the bytes a fresh DeviceWeights load of the same
         tensors builds; data pointers do not change; rows a tensor does not own are not touched.  All pairs are validated before
         anything is written (unknown name: KeyError; wrong shape or a dtype other than bf16 / fp32: ValueError; a layout the
         kernel cannot rewrite: O3VError).  Matrices go through o3v_repack_rows, vectors (norms, biases) through in-place device
