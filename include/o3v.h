@@ -716,6 +716,29 @@ typedef struct {
  * then the write pass).  Bytes equal a fresh DeviceWeights load of the same tensor; rows outside the blocks are not touched. */
 int o3v_repack_rows(const o3v_repack_desc* d, o3v_stream_t stream);
 
+/* ---- LoRA adapter merge (DeviceWeights.load_adapter): W' = bf16(W + scale * B . A), the adapter applied merged so that every
+ * forward kernel stays what it is; peft's `with model.disable_adapter():` (R:grpo_trainer.py:624-630) is a pointer swap -------- */
+#define O3V_LORA_MAX_RANK 256
+typedef struct {
+    const void* base;      /* bf16 packed row image [base_rows][base_ld] the matrix lives in */
+    const void* A;         /* lora_A.weight [r][a_ld], bf16 or f32 (ab_dtype: O3V_SRC_*; f32 is rounded as O3V_SRC_F32 is) */
+    const void* B;         /* lora_B.weight [N][b_ld], same dtype */
+    void* out;             /* bf16 [N][out_ld]; columns >= K are not written */
+    int64_t base_ld, a_ld, b_ld, out_ld;   /* elements; base_ld, a_ld, out_ld >= K and whole 16-byte rows; b_ld >= r */
+    int ab_dtype;
+    int N, K, r;           /* N % 16 == 0, K % 8 == 0, 1 <= r <= O3V_LORA_MAX_RANK (zero-padded to a multiple of 32 inside) */
+    int base_rows;         /* rows of the base image: the last block read must lie inside it */
+    int blk0, blk_stride;  /* matrix row n is base row 16 (blk0 + (n / 16) blk_stride) + n % 16: q / k / v inside qkv_w, the 16-row
+                              gate / up interleave of gu_w (blk_stride 2, blk0 0 / 1) */
+    float scale;           /* finite */
+} o3v_lora_desc;
+/* out[n][k] = bf16_rne( f32(base[row(n)][k]) + scale * sum_j B[n][j] A[j][k] ): products on the bf16 matrix cores with f32
+ * accumulation, scale and the base addition in f32 (a multiply, then an add), ONE rounding at the end (torch's rule).  One launch
+ * on `stream`, no host synchronisation.  O3V_ERR_ARG (null / misaligned pointer, negative size, a pitch below its width, rows
+ * outside the base image, a non-finite scale) or O3V_ERR_SHAPE (r > O3V_LORA_MAX_RANK, N % 16, K % 8, a row pitch that is not whole
+ * 16-byte units) before any launch. */
+int o3v_lora_merge(const o3v_lora_desc* d, o3v_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

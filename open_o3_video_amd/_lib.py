@@ -102,6 +102,14 @@ class RepackDesc(C.Structure):
 
 
 SRC_BF16, SRC_F32 = 0, 1   # O3V_SRC_* in include/o3v.h
+LORA_MAX_RANK = 256        # O3V_LORA_MAX_RANK
+
+
+class LoraDesc(C.Structure):
+    """o3v_lora_desc: one o3v_lora_merge launch."""
+    _fields_ = [(n, vp) for n in ("base", "A", "B", "out")] + [(n, C.c_int64) for n in ("base_ld", "a_ld", "b_ld", "out_ld")] + \
+               [(n, i32) for n in ("ab_dtype", "N", "K", "r", "base_rows", "blk0", "blk_stride")] + [("scale", f32)]
+
 
 # name -> argtypes (return type int unless listed in _RET)
 SIGNATURES = {
@@ -189,6 +197,7 @@ SIGNATURES = {
     "o3v_logprobs_rows": [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp],
     "o3v_llm_decode_lp": [C.POINTER(LlmDesc), C.POINTER(DecodeStateOwn), C.POINTER(LogprobOpts), i32, i32, i32, vp],
     "o3v_repack_rows": [C.POINTER(RepackDesc), vp],
+    "o3v_lora_merge": [C.POINTER(LoraDesc), vp],
     "o3v_sample_step_ex": [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, f32, i32, f32, u64, vp, i32, i32, vp,
                            C.POINTER(LogprobOpts), C.POINTER(SamplingOpts), vp],
     "o3v_llm_decode_ex": [C.POINTER(LlmDesc), C.POINTER(DecodeStateOwn), C.POINTER(LogprobOpts), C.POINTER(SamplingOpts), i32, i32, i32,

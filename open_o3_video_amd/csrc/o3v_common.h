@@ -30,6 +30,13 @@ __device__ __forceinline__ uint32_t pack_bf2(float lo, float hi) {
 // value after a bf16 materialisation
 __device__ __forceinline__ float rbf(float f) { return bf2f(f2bf(f)); }
 
+// torch's float -> bfloat16 (c10 round_to_nearest_even): RNE on the bit pattern, every NaN -> 0x7FC0
+__device__ __forceinline__ uint32_t torch_bf16(float f) {
+    const uint32_t u = __float_as_uint(f);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return 0x7FC0u;
+    return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

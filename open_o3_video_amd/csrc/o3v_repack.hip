@@ -26,13 +26,6 @@
 
 namespace {
 
-// torch's float -> bfloat16 (c10 round_to_nearest_even): RNE on the bit pattern, every NaN -> 0x7FC0
-__device__ __forceinline__ uint32_t torch_bf16(float f) {
-    const uint32_t u = __float_as_uint(f);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return 0x7FC0u;
-    return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
-}
-
 // 16 destination columns c0..c0+15 of source row s (s < 0: a zero row) as 8 packed bf16 pairs.  vec: the widest load the
 // source rows allow (16 or 8 bytes; 0: element loads) -- a row pitch like the ViT down_proj's 3420 bf16 is only 8-byte aligned
 template <bool F32>

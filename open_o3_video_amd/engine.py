@@ -10,6 +10,7 @@ R:eval/models/model_vllm.py:103-126); TF = transformers 5.15.0 models/qwen2_5_vl
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import math
 import os
@@ -1124,6 +1125,57 @@ class O3VEngine:
             self.drop_prompt_handover()
             if self.q3:
                 self._vit_plan_cache.clear()   # the resampled position table lives in the plan
+
+    # ------------------------------------------------------------------------------------------ LoRA adapter
+    def _adapter_state_changed(self):
+        """Nothing computed under one adapter state may be served under another: the same invalidation as load_weights."""
+        self.weights_version += 1
+        self.drop_prefix_cache()
+        self.drop_prompt_handover()
+        if self.q3:
+            self._vit_plan_cache.clear()
+
+    def load_adapter(self, named_tensors, scale=None, lora_alpha=None, use_rslora=False) -> set:
+        """A peft LoRA adapter merged on the device next to the base weights (DeviceWeights.load_adapter) and switched on.  Decoding
+        with it costs what decoding without it costs; `with engine.adapter_disabled():` runs the base (the reference log-probs of
+        R:grpo_trainer.py:624-630).  A later call with the same targets rewrites the adapter images in place: the per-step push of
+        a LoRA trainer moves A and B only."""
+        try:
+            return self.w.load_adapter(named_tensors, scale=scale, lora_alpha=lora_alpha, use_rslora=use_rslora)
+        finally:
+            self._adapter_state_changed()
+
+    def unload_adapter(self):
+        try:
+            self.w.unload_adapter()
+        finally:
+            self._adapter_state_changed()
+
+    def set_adapter_enabled(self, flag: bool):
+        if bool(flag) != self.w.adapter_enabled:
+            try:
+                self.w.set_adapter_enabled(flag)
+            finally:
+                self._adapter_state_changed()
+
+    @property
+    def adapter_loaded(self) -> bool:
+        return self.w.adapter_loaded
+
+    @property
+    def adapter_enabled(self) -> bool:
+        return self.w.adapter_enabled
+
+    @contextlib.contextmanager
+    def adapter_disabled(self):
+        """peft's disable_adapter(): the base weights inside the block, the previous state after it (also on an exception)."""
+        was = self.w.adapter_enabled
+        self.set_adapter_enabled(False)
+        try:
+            yield self
+        finally:
+            if was and self.w.adapter_loaded:
+                self.set_adapter_enabled(True)
 
     # ------------------------------------------------------------------------------------------ logits / logps
     @torch.no_grad()

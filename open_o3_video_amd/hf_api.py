@@ -11,6 +11,7 @@ prompt and fans the KV cache out to the G completions.
 """
 from __future__ import annotations
 
+import json
 import os
 from types import SimpleNamespace
 from typing import List, NamedTuple, Optional
@@ -90,6 +91,38 @@ def resolve_generation_config(passed, model_gc, kwargs, mode: str = "pinned") ->
     return out
 
 
+def read_adapter_config(cfg: dict):
+    """(lora_alpha, use_rslora) of a peft adapter_config.json; what the merged form cannot express is refused by name."""
+    if cfg.get("peft_type", "LORA") != "LORA":
+        raise ValueError(f"adapter_config.json: peft_type {cfg['peft_type']!r} (LoRA adapters only)")
+    if cfg.get("bias", "none") != "none":
+        raise ValueError(f"adapter_config.json: bias={cfg['bias']!r} (only bias='none' is supported)")
+    if cfg.get("use_dora"):
+        raise ValueError("adapter_config.json: use_dora (DoRA adapters are not supported)")
+    for k in ("rank_pattern", "alpha_pattern", "modules_to_save"):
+        if cfg.get(k):
+            raise ValueError(f"adapter_config.json: a non-empty {k} is not supported")
+    if cfg.get("fan_in_fan_out"):
+        raise ValueError("adapter_config.json: fan_in_fan_out (transposed base layers) is not supported")
+    if "lora_alpha" not in cfg:
+        raise ValueError("adapter_config.json: lora_alpha is missing")
+    return float(cfg["lora_alpha"]), bool(cfg.get("use_rslora", False))
+
+
+def read_adapter_dir(path: str):
+    """Local peft adapter directory -> ((name, tensor) pairs, lora_alpha, use_rslora).  Never touches the network."""
+    with open(os.path.join(path, "adapter_config.json")) as f:
+        cfg = json.load(f)
+    alpha, rslora = read_adapter_config(cfg)
+    from safetensors.torch import load_file
+    tensors = load_file(os.path.join(path, "adapter_model.safetensors"))
+    r = cfg.get("r")
+    for name, t in tensors.items():
+        if r is not None and ".lora_A." in name and t.shape[0] != int(r):
+            raise ValueError(f"{name}: rank {t.shape[0]}, adapter_config.json says r = {r}")
+    return list(tensors.items()), alpha, rslora
+
+
 class Qwen2_5_VLForConditionalGeneration:
     def __init__(self, cfg: O3VConfig, engine: O3VEngine):
         self.engine = engine
@@ -153,6 +186,27 @@ class Qwen2_5_VLForConditionalGeneration:
     def load_weights(self, weights) -> set:
         """(name, tensor) pairs in any spelling the checkpoint loader accepts; see O3VEngine.load_weights."""
         return self.engine.load_weights(weights)
+
+    def load_adapter(self, adapter, adapter_name: str = "default", scale=None, lora_alpha=None, use_rslora=False) -> set:
+        """A peft LoRA adapter: a local directory (adapter_config.json + adapter_model.safetensors; r, lora_alpha and use_rslora
+        come from the config) or (name, tensor) pairs with scale / lora_alpha given here.  One adapter is resident; it is merged on
+        the device and enabled (O3VEngine.load_adapter)."""
+        if isinstance(adapter, (str, os.PathLike)):
+            adapter, lora_alpha, use_rslora = read_adapter_dir(os.fspath(adapter))
+            scale = None
+        self.adapter_name = adapter_name
+        return self.engine.load_adapter(adapter, scale=scale, lora_alpha=lora_alpha, use_rslora=use_rslora)
+
+    def unload_adapter(self):
+        self.engine.unload_adapter()
+
+    def disable_adapter(self):
+        """peft's context manager: the base weights inside the block (R:grpo_trainer.py:624-630)."""
+        return self.engine.adapter_disabled()
+
+    @property
+    def adapter_loaded(self) -> bool:
+        return self.engine.adapter_loaded
 
     def load_state_dict(self, state_dict, strict: bool = True):
         """nn.Module.load_state_dict: strict requires every weight of the model and nothing else (RuntimeError otherwise);

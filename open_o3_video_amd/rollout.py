@@ -77,8 +77,10 @@ class RolloutResult:
 
 
 class GroupRollout:
-    """model / ref_model: open_o3_video_amd.hf_api.Qwen2_5_VLForConditionalGeneration (ref_model None -> the policy
-    itself, as the reference's PEFT branch does).  decode: ids -> text (tokenizer.batch_decode)."""
+    """model / ref_model: open_o3_video_amd.hf_api.Qwen2_5_VLForConditionalGeneration.  ref_model None is the reference's PEFT
+    branch (R:grpo_trainer.py:624-630): with a LoRA adapter loaded on `model` the reference log-probs come from `model` under
+    `model.disable_adapter()`, i.e. from the base weights; with no adapter loaded the policy is its own reference (ref = lp, the KL
+    term is identically 0).  decode: ids -> text (tokenizer.batch_decode)."""
 
     def __init__(self, model, reward_funcs: Sequence[Callable], decode: Callable[[torch.Tensor], List[str]],
                  eos_token_id: int, pad_token_id: int, ref_model=None, num_generations: int = 4,
@@ -135,7 +137,14 @@ class GroupRollout:
         # per-token log-probs of the completions under the policy and the reference model (R:…:601-632): the G rows share
         # the prompt, so each model runs the ViT and the prompt once and the lm_head only over the G x T kept positions
         lp = self._logps(self.model, ids, mask, comp, pv, grid, pc, vid)
-        ref = lp if self.ref_model is None else self._logps(self.ref_model, ids, mask, comp, pv, grid, pc, vid)
+        own_ref = self.ref_model is None and not getattr(self.model, "adapter_loaded", False)   # the policy is its own reference
+        if self.ref_model is not None:
+            ref = self._logps(self.ref_model, ids, mask, comp, pv, grid, pc, vid)
+        elif own_ref:
+            ref = lp
+        else:
+            with self.model.disable_adapter():
+                ref = self._logps(self.model, ids, mask, comp, pv, grid, pc, vid)
         kl = per_token_kl(ref, lp)
         texts = self.decode(comp)
         completions = [[{"role": "assistant", "content": t}] for t in texts]
@@ -151,7 +160,7 @@ class GroupRollout:
             comp = o3v_dist.all_gather_padded(comp, T_all, self.pad)
             cmask = o3v_dist.all_gather_padded(cmask, T_all, 0)
             lp = o3v_dist.all_gather_padded(lp, T_all, 0.0)
-            ref = lp if self.ref_model is None else o3v_dist.all_gather_padded(ref, T_all, 0.0)
+            ref = lp if own_ref else o3v_dist.all_gather_padded(ref, T_all, 0.0)
             kl = per_token_kl(ref, lp)
             rpf = o3v_dist.all_gather_records(rpf.contiguous())
             texts = [t for part in o3v_dist.gather_objects(texts) for t in part]

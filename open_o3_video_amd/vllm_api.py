@@ -271,6 +271,29 @@ def decode_quantization(quantization: Optional[str]) -> dict:
     return dict(fp8_decode=quantization in ("fp8", "mxfp4"), mxfp4_decode=quantization == "mxfp4")
 
 
+class LoRARequest:
+    """vllm.lora.request.LoRARequest: a name, a positive id and the local adapter directory (adapter_config.json +
+    adapter_model.safetensors).  Two requests name the same adapter when id and path agree."""
+
+    def __init__(self, lora_name: str, lora_int_id: int, lora_path: str = "", **_):
+        if int(lora_int_id) < 1:
+            raise ValueError(f"id must be > 0, got {lora_int_id}")
+        self.lora_name, self.lora_int_id, self.lora_path = lora_name, int(lora_int_id), lora_path
+
+    @property
+    def key(self):
+        return (self.lora_int_id, self.lora_path)
+
+    def __eq__(self, other):
+        return isinstance(other, LoRARequest) and self.key == other.key
+
+    def __hash__(self):
+        return hash(self.key)
+
+    def __repr__(self):
+        return f"LoRARequest(lora_name={self.lora_name!r}, lora_int_id={self.lora_int_id}, lora_path={self.lora_path!r})"
+
+
 class LLM:
     IMAGE_PAD = "<|image_pad|>"
     VIDEO_PAD = "<|video_pad|>"
@@ -282,7 +305,7 @@ class LLM:
                  min_pixels: int = 56 * 56, max_pixels: int = 14 * 14 * 4 * 1280, device="cuda",
                  enable_prefix_caching: bool = True, quantization: Optional[str] = None, mm_processor_kwargs: Optional[dict] = None,
                  position_mode: str = "pinned", fp8_prefill: bool = False, kv_cache_dtype: str = "auto",
-                 share_video_prefix: bool = False, **_):
+                 share_video_prefix: bool = False, enable_lora: bool = False, max_lora_rank: int = 16, **_):
         # vLLM's keyword: "fp8" / "fp8_e4m3" keep the K/V cache of independent-row decodes as e4m3fn rows with one power-of-two scale
         # per (token, kv head) (O3VEngine.kv_cache_dtype; not vLLM's per-tensor k_scale / v_scale: parity unpinned against vLLM)
         kv_dtypes = {"auto": "bf16", "bfloat16": "bf16", "fp8": "fp8", "fp8_e4m3": "fp8"}
@@ -360,6 +383,42 @@ class LLM:
         # video rope arithmetic: "pinned" = vllm 0.7.2's MRotaryEmbedding.get_input_positions (R:setup.sh:7; restated, parity
         # unpinned), "tf5" = transformers 5.15 (goldens G5b / G14 / G15); see indexing.rope_index
         self.position_mode = position_mode
+        # vLLM's LoRA keywords: generate(lora_request=LoRARequest(...)) runs under that adapter, merged on the device
+        # (O3VEngine.load_adapter); ONE adapter is resident, a request for another (id, path) replaces it
+        self.enable_lora, self.max_lora_rank = bool(enable_lora), int(max_lora_rank)
+        self._lora_resident = None
+
+    def _apply_lora(self, lora_request, n_inputs: int):
+        """Bring the engine into the adapter state a generate call asks for.  Without enable_lora and without a request nothing is
+        touched."""
+        if isinstance(lora_request, (list, tuple)):
+            if len(lora_request) != n_inputs:
+                raise ValueError(f"The lengths of prompts ({n_inputs}) and lora_request ({len(lora_request)}) must be the same.")
+            first = lora_request[0] if lora_request else None
+            for r in lora_request:
+                if (r.key if r is not None else None) != (first.key if first is not None else None):
+                    raise ValueError(f"lora_request: {first!r} and {r!r} in one call; one adapter is resident at a time, so every "
+                                     "request of a generate call must name the same adapter (or none)")
+            lora_request = first
+        if lora_request is None:
+            if self.enable_lora and self.engine.adapter_loaded:
+                self.engine.set_adapter_enabled(False)
+            return
+        if not self.enable_lora:
+            raise ValueError(f"Got lora_request {lora_request} but LoRA is not enabled!")
+        if self._lora_resident != lora_request.key or not self.engine.adapter_loaded:
+            from .hf_api import read_adapter_dir
+            if not os.path.isdir(lora_request.lora_path):
+                raise OSError(f"{lora_request.lora_path} is not a local adapter directory (this build never downloads)")
+            tensors, alpha, rslora = read_adapter_dir(lora_request.lora_path)
+            rank = max((t.shape[0] for n, t in tensors if ".lora_A." in n), default=0)
+            if rank > self.max_lora_rank:
+                raise ValueError(f"{lora_request.lora_name}: LoRA rank {rank} is greater than max_lora_rank {self.max_lora_rank}")
+            self._lora_resident = None
+            self.engine.load_adapter(tensors, lora_alpha=alpha, use_rslora=rslora)
+            self._lora_resident = lora_request.key
+        else:
+            self.engine.set_adapter_enabled(True)
 
     # ---- new policy weights (GRPO / GSPO: the trainer pushes them after every optimizer step)
     def load_weights(self, weights) -> set:
@@ -556,13 +615,15 @@ class LLM:
         self._guides[key] = g
         return g
 
-    def generate(self, inputs, sampling_params=None, use_tqdm: bool = False):
+    def generate(self, inputs, sampling_params=None, use_tqdm: bool = False, lora_request=None):
         """`sampling_params`: one SamplingParams for every request, or a list with one per request.  Requests with equal parameters
         run together exactly as a single-parameter call runs them; results come back in input order, and request ids / default
-        seeds follow the input position, so a request's samples do not depend on what it was grouped with."""
+        seeds follow the input position, so a request's samples do not depend on what it was grouped with.
+        `lora_request` (needs LLM(enable_lora=True)): the adapter the call runs under, None = the base weights."""
         if isinstance(inputs, dict):
             inputs = [inputs]
         inputs = list(inputs)
+        self._apply_lora(lora_request, len(inputs))
         if not isinstance(sampling_params, (list, tuple)):
             return self._generate_group(inputs, sampling_params or SamplingParams(), list(range(len(inputs))))
         if len(sampling_params) != len(inputs):

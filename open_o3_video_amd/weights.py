@@ -15,7 +15,9 @@ from __future__ import annotations
 import ctypes as C
 import glob
 import json
+import math
 import os
+import re
 from typing import Callable, Dict
 
 import torch
@@ -196,6 +198,21 @@ class _VectorWrite:
         return 2 * (t[self.slot][self.dst].numel() if isinstance(self.dst, slice) else self.dst.numel())
 
 
+class _LoraTarget:
+    """One adapted matrix: A [r, K8] and B [N16, r] as the device keeps them (zero-padded to whole 16-row blocks / 8-column chunks,
+    which adds exact zeros), its scale and the plan entry whose write places the merged matrix."""
+
+    def __init__(self, name, entry, A, B, scale):
+        self.name, self.entry, self.A, self.B, self.scale = name, entry, A, B, float(scale)
+        self.r = A.shape[0]
+
+
+_LORA_KEY = re.compile(r"^(?:base_model\.model\.)?(?P<mod>.+)\.lora_(?P<ab>[AB])(?:\.(?P<adapter>[^.]+))?\.weight$")
+# matrices the update plan could rewrite but that no LoRA linear wraps
+_LORA_NOT_LINEAR = (("lm_head.weight", "lm_head"), ("embed_tokens.weight", "embed_tokens (an embedding: lora_embedding_* is not supported)"),
+                    ("patch_embed.proj.weight", "the patch-embed convolution"), ("pos_embed.weight", "the position table (an embedding)"))
+
+
 class UpdateEntry:
     """What load_weights does with one HF name: its expected shape (alt_shapes: other accepted views, the Conv3d patch weight)
     and the writes that put it where DeviceWeights packed it."""
@@ -328,6 +345,10 @@ class DeviceWeights:
                 self.llm.lm_head8p = keep["l.head8p"].data_ptr()
         self._check_shapes()
         self._record_update_plan()
+        # LoRA adapter (load_adapter): canonical name -> _LoraTarget, and the adapter's own copy of every image of the slots it touches
+        self._adapter_targets: Dict[str, "_LoraTarget"] = {}
+        self.adapter_t: Dict[str, torch.Tensor] = {}
+        self._adapter_on = False
 
     def _pack_vision(self, v):
         """Qwen2.5-VL tower (TF:408-471)."""
@@ -627,8 +648,195 @@ class DeviceWeights:
                     t.record_stream(stream)
                 for w in e.writes:
                     w.apply(self.t, t.reshape(e.shape), stream)
+                    if key not in self._adapter_targets and getattr(w, "slot", None) in self.adapter_t:
+                        w.apply(self.adapter_t, t.reshape(e.shape), stream)   # an untargeted matrix of an adapted slot: the base's rows
                 done.add(key)
+            self._merge_adapter([k for k in self._adapter_targets if k in done], stream)   # adapter images are never stale
         return done
+
+    # ------------------------------------------------------------------------------------ LoRA adapter (merged, switchable)
+    def _validate_adapter(self, named_tensors, scale=None, lora_alpha=None, use_rslora=False):
+        """peft names -> [(canonical name, plan entry, A, B, scale)], every refusal raised by name before anything is allocated."""
+        pairs: Dict[str, dict] = {}
+        adapters = set()
+        for name, t in named_tensors:
+            if "lora_magnitude_vector" in name:
+                raise ValueError(f"{name}: DoRA adapters (lora_magnitude_vector) are not supported")
+            if "lora_embedding_" in name:
+                raise ValueError(f"{name}: LoRA on embeddings (lora_embedding_*) is not supported")
+            if "modules_to_save" in name:
+                raise ValueError(f"{name}: modules_to_save tensors are full weights, not an adapter: send them through load_weights")
+            m = _LORA_KEY.match(name)
+            if m is None:
+                raise ValueError(f"{name}: not a LoRA tensor name (<module>.lora_A[.<adapter>].weight / lora_B)")
+            if not torch.is_tensor(t) or t.dtype not in (torch.bfloat16, torch.float32):
+                raise ValueError(f"{name}: dtype {getattr(t, 'dtype', type(t))} (bf16 or fp32 adapters only)")
+            if t.dim() != 2:
+                raise ValueError(f"{name}: shape {tuple(t.shape)}, a LoRA factor is a matrix")
+            adapters.add(m["adapter"])
+            if len(adapters) > 1:
+                raise ValueError(f"{name}: tensors of several adapters ({sorted(str(a) for a in adapters)}); one adapter is resident at a time")
+            slot = pairs.setdefault(m["mod"], {})
+            if m["ab"] in slot:
+                raise ValueError(f"{name}: lora_{m['ab']} of {m['mod']} given twice")
+            slot[m["ab"]] = (name, t.detach())
+        if scale is None and lora_alpha is None:
+            raise ValueError("load_adapter needs scale or lora_alpha")
+        out = []
+        for mod, ab in pairs.items():
+            if "A" not in ab or "B" not in ab:
+                have = ab.get("A") or ab.get("B")
+                raise ValueError(f"{have[0]}: {mod} has lora_{'A' if 'A' in ab else 'B'} without lora_{'B' if 'A' in ab else 'A'}")
+            key = self.resolve_name(mod + ".weight")     # KeyError: the engine has no such module
+            e = self.update_plan[key]
+            for suffix, what in _LORA_NOT_LINEAR:
+                if key.endswith(suffix):
+                    raise ValueError(f"{mod}: no LoRA on {what}")
+            if e.unsupported:
+                raise ValueError(f"{mod}: no in-place update for this layout ({e.unsupported})")
+            w = e.writes[0] if len(e.writes) == 1 else None
+            if not isinstance(w, _RepackWrite) or len(e.shape) != 2:
+                raise ValueError(f"{mod}: not a linear layer's matrix")
+            if w.row_map is not None or w.col_map is not None:
+                raise ValueError(f"{mod}: its rows / columns are re-ordered in the packed image (Qwen3-VL tower attention); LoRA on it is "
+                                 "not supported")
+            (an, A), (bn, B) = ab["A"], ab["B"]
+            N, K = e.shape
+            r = A.shape[0]
+            if r < 1 or tuple(A.shape) != (r, K) or tuple(B.shape) != (N, r):
+                raise ValueError(f"{mod}: lora_A {tuple(A.shape)} / lora_B {tuple(B.shape)} do not factor the engine's {e.shape} at one rank")
+            if r > _lib.LORA_MAX_RANK:
+                raise ValueError(f"{mod}: rank {r} > {_lib.LORA_MAX_RANK}")
+            rows = self.t[w.slot].shape[0]
+            n16 = (N + 15) // 16
+            if 16 * (w.row0 + (n16 - 1) * w.stride) + 16 > rows:
+                raise ValueError(f"{mod}: {w.slot} keeps {rows} rows, not whole 16-row blocks of this matrix")
+            sc = float(scale) if scale is not None else float(lora_alpha) / (math.sqrt(r) if use_rslora else r)
+            if not math.isfinite(sc):
+                raise ValueError(f"{mod}: scale {sc}")
+            out.append((key, e, A, B, sc))
+        if not out:
+            raise ValueError("load_adapter: no LoRA tensors given")
+        return out
+
+    def adapter_image_keys(self, target_names) -> list:
+        """Keys of self.t an adapter on these plan entries owns a copy of: each touched slot and every image derived from it."""
+        keys = []
+        for name in target_names:
+            w = self.update_plan[self.resolve_name(name)].writes[0]
+            for k in (w.slot, w.frag, w.q8, w.q8s, w.q8frag, w.q4, w.q4s, w.q4frag, w.q4frags):
+                if k and k not in keys:
+                    keys.append(k)
+        return keys
+
+    def _descriptor_field(self, key):
+        """(ctypes structure, field) the kernels read image `key` through."""
+        m = re.fullmatch(r"l(\d+)\.(qkv|o|gu|down)_w(p|8|8s|8p|4|4s|4p|4ps)?", key)
+        if m:
+            n = m[2]
+            field = {None: n + "_w", "p": n + "_wp", "8": n + "_w8", "8s": n + "_s", "8p": n + "_w8p", "4": n + "_w4", "4s": n + "_s4",
+                     "4p": n + "_w4p", "4ps": n + "_s4p"}[m[3]]
+            return self.llm_layers[int(m[1])], field
+        m = re.fullmatch(r"v(\d+)\.(\w+_w)", key)
+        if m:
+            return (self.vit3_blocks if self.vit3 is not None else self.vit_blocks)[int(m[1])], m[2]
+        if key in ("v.m0_w", "v.m2_w"):
+            return self.vit, key[2:]
+        m = re.fullmatch(r"v\.m\.(fc[12]_w)", key)
+        if m:
+            return self.vit3.merger, m[1]
+        m = re.fullmatch(r"v\.ds(\d+)\.(fc[12]_w)", key)
+        if m:
+            return self.vit3.deep[int(m[1])], m[2]
+        raise KeyError(key)
+
+    @property
+    def adapter_loaded(self) -> bool:
+        return bool(self._adapter_targets)
+
+    @property
+    def adapter_enabled(self) -> bool:
+        return self._adapter_on
+
+    def adapter_bytes(self) -> int:
+        """HBM the adapter holds: its image copies plus A and B."""
+        n = sum(t.numel() * t.element_size() for t in self.adapter_t.values())
+        return n + sum(x.numel() * x.element_size() for tg in self._adapter_targets.values() for x in (tg.A, tg.B))
+
+    def load_adapter(self, named_tensors, scale=None, lora_alpha=None, use_rslora=False) -> set:
+        """A peft LoRA adapter, applied MERGED next to the base: for every adapted matrix W' = bf16(W + s B A) (o3v_lora_merge: fp32
+        accumulation, one rounding) is packed by that matrix's own o3v_repack_rows write into the adapter's copy of every image its
+        slot keeps, and the descriptors are pointed at the copies -- every forward kernel runs unchanged and at the base's cost.
+        Names: [base_model.model.]<HF module path>.lora_A[.<adapter name>].weight and lora_B; s = scale, or lora_alpha / r
+        (lora_alpha / sqrt(r) with use_rslora).  Targets are the linears whose packed rows and columns keep their order (the 7 LLM
+        linears, the Qwen2.5-VL tower's linears, the mergers, Qwen3-VL's fc1 / fc2); everything else is refused by name with
+        ValueError before anything is allocated or written.  A load with the targets of the resident adapter reuses its images
+        (stable data pointers: the trainer's per-step push); the copies start as the base's bytes, so rows of an untargeted matrix
+        sharing a slot equal the base.  The base images are never written.  Leaves the adapter enabled; returns the canonical
+        names adapted.  Engine caches are the caller's (O3VEngine.load_adapter)."""
+        items = self._validate_adapter(named_tensors, scale, lora_alpha, use_rslora)
+        if self.device.type != "cuda":
+            raise _lib.O3VError("load_adapter merges on the device: it needs weights on a ROCm GPU")
+        target = self.t["l.embed"].device
+        stream = torch.cuda.current_stream(target)
+        names = {key for key, *_ in items}
+        with torch.cuda.device(target):
+            if names != set(self._adapter_targets):
+                self.unload_adapter()
+                for k in self.adapter_image_keys(names):
+                    self.adapter_t[k] = self.t[k].clone()
+            self._adapter_targets = {}
+            for key, e, A, B, sc in items:
+                N, K = e.shape
+                dt = torch.float32 if torch.float32 in (A.dtype, B.dtype) else torch.bfloat16
+                if K % 8 == 0 and N % 16 == 0:      # the usual case: one private copy each, no padding
+                    Ap = A.to(device=target, dtype=dt, copy=True).contiguous()
+                    Bp = B.to(device=target, dtype=dt, copy=True).contiguous()
+                else:
+                    Ap = torch.zeros((A.shape[0], (K + 7) // 8 * 8), dtype=dt, device=target)
+                    Bp = torch.zeros(((N + 15) // 16 * 16, A.shape[0]), dtype=dt, device=target)
+                    Ap[:, :K].copy_(A)
+                    Bp[:N].copy_(B)
+                self._adapter_targets[key] = _LoraTarget(key, e, Ap, Bp, sc)
+            self._merge_adapter(list(self._adapter_targets), stream)
+        self.set_adapter_enabled(True)
+        return names
+
+    def _merge_adapter(self, names, stream):
+        """o3v_lora_merge of each named target into one staging tensor (the largest target), then its plan entry's repack into the
+        adapter images."""
+        if not names:
+            return
+        tgs = [self._adapter_targets[n] for n in names]
+        stage = torch.empty(max(tg.B.shape[0] * tg.A.shape[1] for tg in tgs), dtype=torch.bfloat16, device=tgs[0].A.device)
+        for tg in tgs:
+            w, (N, K) = tg.entry.writes[0], tg.entry.shape
+            base = self.t[w.slot]
+            n16, k8 = tg.B.shape[0], tg.A.shape[1]
+            out = stage[: n16 * k8].view(n16, k8)
+            d = _lib.LoraDesc(base=base.data_ptr(), A=tg.A.data_ptr(), B=tg.B.data_ptr(), out=out.data_ptr(), base_ld=base.stride(0),
+                              a_ld=tg.A.stride(0), b_ld=tg.B.stride(0), out_ld=k8,
+                              ab_dtype=_lib.SRC_F32 if tg.A.dtype == torch.float32 else _lib.SRC_BF16, N=n16, K=k8, r=tg.r,
+                              base_rows=base.shape[0], blk0=w.row0, blk_stride=w.stride, scale=tg.scale)
+            _lib.call("o3v_lora_merge", C.byref(d), C.c_void_p(stream.cuda_stream))
+            w.apply(self.adapter_t, out[:N, :K], stream)
+
+    def set_adapter_enabled(self, flag: bool):
+        """Point the descriptor fields of the adapted slots at the adapter's images (True) or at the base's (False).  Host only:
+        launches already queued keep the pointers they were given."""
+        flag = bool(flag)
+        if flag and not self._adapter_targets:
+            raise ValueError("set_adapter_enabled(True): no adapter is loaded")
+        src = self.adapter_t if flag else self.t
+        for key in self.adapter_t:
+            st, field = self._descriptor_field(key)
+            setattr(st, field, src[key].data_ptr())
+        self._adapter_on = flag
+
+    def unload_adapter(self):
+        """Back to the base images; the adapter's memory is released."""
+        self.set_adapter_enabled(False)
+        self._adapter_targets, self.adapter_t = {}, {}
 
     def update_bytes(self, names=None):
         """(bytes read, bytes written) of a bf16-source update of `names` (default: every plan entry)."""
