@@ -39,10 +39,14 @@ typedef struct ihipStream_t* o3v_stream_t; /* hipStream_t */
 int o3v_abi_version(void);
 
 /* ---- elementwise / layout (HBM-bound) ------------------------------------------------------------------- */
-/* Qwen2_5_VLRMSNorm.forward, TF:65-79 */
+/* Qwen2_5_VLRMSNorm.forward, TF:65-79.  x, out bf16 rows of pitch ld_in / ld_out elements (out may be x); the pitches are taken as
+ * given -- ld >= cols is the caller's obligation and is NOT checked (the row quantisers below do check it).  Rows move as
+ * 16-byte chunks: cols, ld_in and ld_out are multiples of 8 (O3V_ERR_ARG otherwise) and x, w, out 16-byte aligned; a row is held
+ * in registers: cols <= 8192 (O3V_ERR_SHAPE above).  Nothing outside [rows, cols] of out is written. */
 int o3v_rmsnorm(const void* x, const void* w, void* out, int rows, int cols, int ld_in, int ld_out, float eps,
                 o3v_stream_t stream);
-/* nn.LayerNorm with bias over `cols` (TF3:122-135, :268-284): fp32 statistics, one rounding.  x,out bf16 [rows, ld]. */
+/* nn.LayerNorm with bias over `cols` (TF3:122-135, :268-284): fp32 statistics, one rounding.  x,out bf16 [rows, ld]; pitches,
+ * alignment and the 8192-column limit as o3v_rmsnorm (same codes). */
 int o3v_layernorm(const void* x, const void* w, const void* b, void* out, int rows, int cols, int ld_in, int ld_out, float eps,
                   o3v_stream_t stream);
 /* apply_rotary_pos_emb_vision, TF:160-171, in place on the q,k thirds of qkv[P,3*H*D]; cos/sin fp32 [P,D/2] */
@@ -100,6 +104,13 @@ int o3v_crop_resize_bilinear(const void* frames, const int* boxes, void* out, in
 int o3v_content_hash128(const void* data, size_t bytes, unsigned long long* out, o3v_stream_t stream);
 
 /* ---- GEMMs ------------------------------------------------------------------------------------------------ */
+/* Pitches of every linear below, in elements: lda / ldx / ldw are the row pitches of the operands that are read in 16-byte chunks --
+ * multiples of 8 (16 for the fp8 operands of o3v_gemm_fp8, in bytes; O3V_ERR_SHAPE otherwise), >= K, base pointers 16-byte aligned.
+ * ldo / ldr (output, residual) are ANY pitch >= the output width, with any N: where N, ldo and (with a residual) ldr are all
+ * multiples of 8 the MFMA GEMMs move 16 bytes per lane (out, res and bias are then 16-byte aligned), otherwise single elements;
+ * the decode linears always store single elements.  Same operations in the same order: the bits do not depend on the pitches.
+ * No entry writes outside [M, N] of out (N/2 columns with O3V_EPI_SWIGLU) or reads outside [M, K] / [N, K] / [M, N] of its
+ * operands; rows past a ragged tile edge re-read a valid row.  res may be out (updated in place, same pitch). */
 /* nn.Linear: out[M,N] = epi(A[M,K] . W[N,K]^T + bias); K % 64 == 0.  MFMA path (ViT, merger, prefill). */
 int o3v_gemm_bf16(const void* A, const void* W, const void* bias, const void* res, void* out, int M, int N, int K, int lda,
                   int ldw, int ldo, int ldr, int epilogue, o3v_stream_t stream);
@@ -115,13 +126,14 @@ int o3v_gemm_bf16_phased(const void* A, const void* W, const void* bias, const v
                          int ldw, int ldo, int ldr, int epilogue, o3v_stream_t stream);
 /* o3v_gemm_bf16 for row counts too small to fill the chip with 128x128 output tiles (a prompt suffix behind a cached
  * prefix: 9..128 rows): K split over `splits` blocks per tile, fp32 partials in `workspace` (splits*M*N floats), reduced
- * in split order.  Epilogues NONE / RESIDUAL / GELU. */
+ * in split order.  Epilogues NONE / RESIDUAL / GELU (another one: O3V_ERR_ARG).  splits > K/64 is clamped; ws_bytes too small:
+ * O3V_ERR_WORKSPACE.  The workspace needs no initialisation: every partial that is summed is written first. */
 int o3v_gemm_bf16_splitk(const void* A, const void* W, const void* bias, const void* res, void* out, int M, int N, int K,
                          int lda, int ldw, int ldo, int ldr, int epilogue, int splits, float* workspace, size_t ws_bytes,
                          o3v_stream_t stream);
 /* same contract for M <= 32 rows (decode): weight-streaming GEMV up to 3 rows, matrix-core skinny GEMM from 4 rows on
  * (9..32 rows need K % 32 == 0 and N % 16 == 0; 17..32 rows run two 16-row column blocks per streamed weight fragment and
- * take no fused norm: normalise with o3v_rmsnorm first). */
+ * take no fused norm: normalise with o3v_rmsnorm first).  K % 8 == 0; ldx, ldw multiples of 8 (O3V_ERR_SHAPE), any ldo / ldr. */
 int o3v_gemv_bf16(const void* X, const void* W, const void* bias, const void* res, void* out, int M, int N, int K, int ldx,
                   int ldw, int ldo, int ldr, int epilogue, o3v_stream_t stream);
 
@@ -149,26 +161,30 @@ int o3v_linear_decode(const void* X, const void* norm_w, float eps, const void* 
  * rows of already normalised X, Wp the fragment-major image, N <= 4096.  The waves that draw the last M tickets of the launch
  * normalise one row each once every part of `out` is in memory; h is bit-identical to o3v_rmsnorm(out, next_norm_w).  sync: the
  * zeroed buffer of o3v_decode_sync_bytes() (lines of its own; the sticky time-out word at O3V_SYNC_TMO_BYTE is shared), epoch = 1,
- * 2, ... counts the calls made on it.  O3V_ERR_SHAPE when the form does not apply (not gfx950, shapes): issue o3v_linear_decode +
- * o3v_rmsnorm instead. */
+ * 2, ... counts the calls made on it.  The normalising waves read `out` and write h in 16-byte chunks: N % 16 == 0 and ldo, ldh
+ * (and ldx) multiples of 8; ldr is any pitch.  O3V_ERR_SHAPE when the form does not apply (not gfx950, those alignments, fewer
+ * than M storing waves -- there is one per 16 columns of N): issue o3v_linear_decode + o3v_rmsnorm instead. */
 int o3v_linear_decode_norm_next(const void* X, const void* Wp, const void* res, void* out, int M, int N, int K, int ldx, int ldo,
                                 int ldr, const void* next_norm_w, float eps, void* h, int ldh, uint32_t* sync, uint32_t epoch,
                                 o3v_stream_t stream);
 
 /* Decode linears on fp8 (OCP e4m3fn) weights, M <= 3 rows: W8 uint8 [N, K] (K % 16 == 0) with one fp32 scale per output
  * row; out = epi(scale[n] * (rmsnorm(X; norm_w) . fp8(W8[n])) + bias), x and the accumulation as in the bf16 path (the fp8
- * values are widened to bf16 exactly, v_cvt_scalef32_pk_bf16_fp8, and meet x in v_dot2c_f32_bf16).  Same epilogues. */
+ * values are widened to bf16 exactly, v_cvt_scalef32_pk_bf16_fp8, and meet x in v_dot2c_f32_bf16).  Same epilogues, any N.
+ * ldx % 8 == 0; more than 3 rows: O3V_ERR_SHAPE (o3v_linear_decode_fp8_rows takes them). */
 int o3v_linear_decode_fp8(const void* X, const void* norm_w, float eps, const void* W8, const float* scale, const void* bias,
                           const void* res, void* out, int M, int N, int K, int ldx, int ldo, int ldr, int epilogue,
                           o3v_stream_t stream);
 /* fp8 rows for 4 <= M <= 32 rows of already normalised x (batched decode, N = 16 self-consistency chains of BASELINE config #5):
  * W8p is the fragment-major fp8 image [N/16][K/64][64][16 B] of the matrix; the weights are widened exactly to bf16 in registers
  * and multiplied on the bf16 matrix cores, the row scale multiplies the fp32 sum.  Epilogues NONE / RESIDUAL / SWIGLU.
- * K % 64 == 0, N % 16 == 0 (SWIGLU: N % 32 == 0). */
+ * K % 64 == 0, N % 16 == 0 (SWIGLU: N % 32 == 0), ldx % 8 == 0: O3V_ERR_SHAPE otherwise; M outside 4..32: O3V_ERR_ARG. */
 int o3v_linear_decode_fp8_rows(const void* X, const void* W8p, const float* scale, const void* bias, const void* res, void* out,
                                int M, int N, int K, int ldx, int ldo, int ldr, int epilogue, o3v_stream_t stream);
 /* q/k/v on fp8 rows for 4..32 rows of already normalised x: bias, M-RoPE and the cache append in the epilogue (the arguments of
- * o3v_gemv_norm_qkv_rope without the fused norm; W8p fragment-major as above). */
+ * o3v_gemv_norm_qkv_rope without the fused norm; W8p fragment-major as above; fewer than 4 rows: O3V_ERR_ARG).
+ * o3v_gemv_norm_qkv_rope_fp8: the same projection with the fused norm on the row-major fp8 rows, M <= 3 (more: O3V_ERR_SHAPE).
+ * Both: ldx % 8 == 0; q and the cache are dense, only slot `slot` of each cache row is written. */
 int o3v_qkv_rope_fp8_rows(const void* X, const void* W8p, const float* scale, const void* bias, int M, int K, int ldx, const void* cosT,
                           const void* sinT, void* qout, void* kcache, void* vcache, int slot, int Hq, int Hkv, int D, int Tmax,
                           int cs_stride_row, int cs_off, o3v_stream_t stream);
@@ -182,6 +198,7 @@ int o3v_gemv_norm_qkv_rope_fp8(const void* X, const void* norm_w, float eps, con
  * W4 uint8 [N, K/2], S4 uint8 [N, K/32], K % 32 == 0.  M <= 3 rows (else O3V_ERR_ARG): out = epi(rmsnorm(X; norm_w) . mxfp4(W4, S4)[n]
  * + bias), x and the accumulation as in the bf16 path -- the codes are widened to bf16 exactly with their block scale applied
  * (v_cvt_scalef32_pk_bf16_fp4) and meet x in v_dot2c_f32_bf16; no per-row scale multiplies the sum.  norm_w may be NULL.
+ * ldx % 8 == 0, ldx >= K, W4 16-byte aligned (O3V_ERR_SHAPE otherwise); any N, ldo, ldr.
  * Epilogues NONE / RESIDUAL / SWIGLU (W4 then holds the interleaved gate/up matrix, N % 32 == 0). */
 int o3v_linear_decode_mxfp4(const void* X, const void* norm_w, float eps, const void* W4, const void* S4, const void* bias,
                             const void* res, void* out, int M, int N, int K, int ldx, int ldo, int ldr, int epilogue,
@@ -190,12 +207,14 @@ int o3v_linear_decode_mxfp4(const void* X, const void* norm_w, float eps, const 
  * [N/16][K/128][64 lanes][16 B] -- lane l of (row block, 128-wide k step t) holds the MX block of row l & 15, k = 128 t + 32 (l >> 4)
  * .. + 32 -- and S4p [N/16][ceil(K/512)][64 lanes][4 B], the same lane's scale bytes of steps 4 q .. 4 q + 3 (padding bytes past
  * K/128 are never read).  Widened in registers as above, multiplied on the bf16 matrix cores (v_mfma_f32_16x16x32_bf16).
- * Epilogues NONE / RESIDUAL / SWIGLU.  K % 128 == 0, N % 16 == 0 (SWIGLU: N % 32 == 0). */
+ * Epilogues NONE / RESIDUAL / SWIGLU.  K % 128 == 0, N % 16 == 0 (SWIGLU: N % 32 == 0), ldx % 8 == 0, ldx >= K, W4p 16-byte and S4p
+ * 4-byte aligned: O3V_ERR_SHAPE otherwise. */
 int o3v_linear_decode_mxfp4_rows(const void* X, const void* W4p, const void* S4p, const void* bias, const void* res, void* out, int M,
                                  int N, int K, int ldx, int ldo, int ldr, int epilogue, o3v_stream_t stream);
 /* bf16 rows [rows, cols] (row pitch ld_in elements) -> MXFP4 codes uint8 [rows, cols/2] + scales uint8 [rows, cols/32], both dense.
  * Per block: e = floor(log2(amax)) - 2 clamped to [-125, 125] (an all-zero block: e = 0), scale byte e + 127, codes = v / 2^e
- * rounded to nearest even on {0, 0.5, 1, 1.5, 2, 3, 4, 6}, saturating at 6, bit 3 = sign.  cols % 32 == 0, ld_in % 8 == 0. */
+ * rounded to nearest even on {0, 0.5, 1, 1.5, 2, 3, 4, 6}, saturating at 6, bit 3 = sign.  cols % 32 == 0, ld_in % 8 == 0
+ * (O3V_ERR_SHAPE otherwise); ld_in >= cols, x and codes 16-byte aligned (O3V_ERR_ARG otherwise).  Any number of columns. */
 int o3v_quantize_rows_mxfp4(const void* x, void* codes, void* scales, int rows, int cols, int ld_in, o3v_stream_t stream);
 
 /* ---- attention ---------------------------------------------------------------------------------------------- */
@@ -273,13 +292,16 @@ int o3v_decode_attn_block(void* x, const void* ln_w, float eps, const void* qkv_
 
 /* ---- fp8 x fp8 on the matrix cores (o3v_fp8.hip): the compute-bound linears as W8A8 (vLLM's fp8 linear method for the checkpoints the
  * reference serves with quantization="fp8"; BASELINE config #5).  OCP e4m3fn; every scale is a power of two. ---- */
-/* q[r, :] = fp8(x[r, :] / scale[r]) with scale[r] = the smallest power of two that brings row r into +-448 (1 for a zero row). */
+/* q[r, :] = fp8(x[r, :] / scale[r]) with scale[r] = the smallest power of two that brings row r into +-448 (1 for a zero row).
+ * x bf16 rows of pitch ld_in, q bytes of pitch ld_q, scale dense [rows].  cols, ld_in and ld_q are multiples of 8 and >= cols
+ * (O3V_ERR_ARG otherwise); any number of columns. */
 int o3v_quantize_rows_fp8(const void* x, void* q, float* scale, int rows, int cols, int ld_in, int ld_q, o3v_stream_t stream);
 /* The same on y = RMSNorm(x) * w with o3v_rmsnorm's arithmetic (TF:65-79): the bf16 values the bf16 path would feed its linears. */
 int o3v_rmsnorm_quantize_fp8(const void* x, const void* w, void* q, float* scale, int rows, int cols, int ld_in, int ld_q, float eps,
                              o3v_stream_t stream);
 /* out[M, N] = epilogue((A8[M, K] . W8[N, K]^T) * sa[m] * sw[n] + bias) on v_mfma_scale_f32_16x16x128_f8f6f4 (unit block scales), fp32
- * accumulation; epilogue O3V_EPI_NONE / _RESIDUAL / _SWIGLU as o3v_gemm_bf16.  K % 128 == 0, lda / ldw in bytes (= elements). */
+ * accumulation; epilogue O3V_EPI_NONE / _RESIDUAL / _SWIGLU as o3v_gemm_bf16.  K % 128 == 0, lda / ldw in bytes (= elements):
+ * multiples of 16, >= K (O3V_ERR_SHAPE otherwise); ldo / ldr as o3v_gemm_bf16. */
 int o3v_gemm_fp8(const void* A8, const float* sa, const void* W8, const float* sw, const void* bias, const void* res, void* out, int M,
                  int N, int K, int lda, int ldw, int ldo, int ldr, int epilogue, o3v_stream_t stream);
 /* o3v_gemm_fp8 with the schedule chosen by the caller (tests, A/B): 0 = the library's choice (the phased kernel wherever K has an even

@@ -223,7 +223,7 @@ _lib = None
 
 
 class O3VError(RuntimeError):
-    pass
+    code = None  # the O3V_ERR_* value when a call of the library returned one
 
 
 def load():
@@ -249,7 +249,9 @@ def load():
 
 def check(rc: int, what: str):
     if rc != OK:
-        raise O3VError(f"{what} failed: {_ERR.get(rc, rc)} ({rc})")
+        err = O3VError(f"{what} failed: {_ERR.get(rc, rc)} ({rc})")
+        err.code = rc
+        raise err
 
 
 def call(name: str, *args):
