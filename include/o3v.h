@@ -246,6 +246,25 @@ int o3v_attn_tiles_prefix(const void* Q, const void* K, const void* V, const voi
 int o3v_attn_decode(const void* Q, const void* Kc, const void* Vc, void* out, float* part_o, float* part_ml,
                     const int* k_lo, int B, int Hq, int Hkv, int D, int ctx, int Tmax, int nsplit, float scale,
                     o3v_stream_t stream);
+/* The same with a context per row (continuous batching).  Kc / Vc bf16 [B][Hkv][Tmax][D] of ONE layer, Knew / Vnew bf16
+ * [B][Hkv][D] the staging rows of the newest token, row_base device i32 [B]: row b's context is ctx_b = row_base[b] + step + 1.
+ * LIVE rows (1 <= ctx_b <= Tmax): the kernel stores Knew / Vnew[b][hk] to slot ctx_b - 1 -- exactly one wave per (b, kv head), the
+ * one whose key range holds the slot; plain vector stores, ordered before that workgroup's own loads by a barrier -- and the row
+ * attends over keys [0, ctx_b), its nsplit splits cut from ITS ctx_b by the arithmetic o3v_attn_decode applies to ctx.  Both forms
+ * instantiate the bodies of o3v_attn_decode's kernels and the merge is the same kernel, so out[b] is bit-identical to
+ * o3v_attn_decode (B = 1, same nsplit, no k_lo) on row b's cache with the staging row already at slot ctx_b - 1; the error bound is
+ * o3v_attn_decode's.
+ * IDLE rows (any other ctx_b: a retired row, an empty slot, a row past its capacity): nothing of the row's cache is read or
+ * written, and its rows of `out` are +0 even when part_o / part_ml arrive holding NaN.
+ * What may be read and is masked: keys >= ctx_b are clamped onto slot ctx_b - 1, so no byte at or behind slot ctx_b is read; slot
+ * ctx_b - 1 is read only after the store above.  Only the appending wave's last tile reaches slot ctx_b - 1 (scalar form: the
+ * waves of the appending workgroup, behind the barrier).  Stale bytes there, NaN included, never reach a sum.
+ * nsplit > 0: the matrix-core form at D == 128; nsplit < 0, and D == 32 / 64 with either sign: the scalar form.
+ * O3V_ERR_ARG: a null pointer, step < 0, Hq % Hkv != 0, nsplit outside +-1..64.  O3V_ERR_SHAPE: Hq / Hkv > 8, D not in 32, 64, 128.
+ * Nothing is launched after an error. */
+int o3v_attn_decode_ragged(const void* Q, void* Kc, void* Vc, const void* Knew, const void* Vnew, void* out, float* part_o,
+                           float* part_ml, const int* row_base, int step, int B, int Hq, int Hkv, int D, int Tmax, int nsplit,
+                           float scale, o3v_stream_t stream);
 /* The same for B = (B/G) groups of G rows whose first `prefix_len` keys are identical (the G completions of one
  * prompt: `num_return_sequences`, R:grpo_trainer.py:306-313, TF:1493-1579 `_expand_inputs_for_generation`; the n
  * samples of R:eval/tts.py:47-123).  The prefix K/V are read ONCE per group, from the cache row of the group's first
@@ -648,6 +667,17 @@ typedef struct {
      * A zeroed pair is the behaviour of before. */
     int own_past;
     const int* own_lo;
+    /* optional ragged regime (continuous batching; read ONLY when flags has O3V_DECODE_RAGGED, so a caller built against the struct
+     * that ends at own_lo stays valid).  row_base [B] device: non-NULL selects the regime.  Row b's context at decode step `step` is
+     * ctx_b = row_base[b] + step + 1 and its cache starts at slot 0 whatever the other rows hold; the row is live iff
+     * 1 <= ctx_b <= Tmax, any other row is idle (o3v_attn_decode_ragged): the host retires a row by writing a large negative base.
+     * kstage / vstage: bf16 staging rows [B][Hkv][1][D], one layer's worth reused by every layer: q/k/v writes the new token's K/V
+     * there (slot 0, capacity 1 -- every q/k/v form, as under k8) and the attention kernel appends it to layer l of kcache / vcache.
+     * The attention half runs on the stand-alone kernels; S and k_lo are not read; the loop's capacity refusal does not apply (rows
+     * guard themselves).  O3V_ERR_ARG before any launch: together with group > 1, kprefix, k8, own_past / own_lo,
+     * O3V_DECODE_KV8_EMULATE, or without both stage pointers.  A zeroed set is the behaviour of before. */
+    const int* row_base;
+    void *kstage, *vstage;
 } o3v_decode_state;
 /* o3v_decode_state.flags.  LAYER_BLOCK: batch-1 bf16 decode may use the persistent layer block (o3v_decode_layer_block) where its
  * shapes allow, then one launch for the attention half + gate/up and one for down_proj per layer; otherwise o3v_decode_attn_block +
@@ -661,6 +691,7 @@ typedef struct {
 #define O3V_DECODE_NO_TAIL_NORM 2
 #define O3V_DECODE_NO_QKV_FUSED_NORM 4
 #define O3V_DECODE_KV8_EMULATE 8
+#define O3V_DECODE_RAGGED 16 /* the struct carries row_base / kstage / vstage behind own_lo */
 
 /* ---- opt-in fp8 K/V cache of the independent-row decode (vLLM kv_cache_dtype="fp8"; head_dim 128) --------------------------------
  * Storage: codes u8 [heads][Tmax][128] (OCP e4m3fn) + scales f32 [heads][Tmax], heads = (layers x) B x Hkv; 132 bytes per

@@ -74,6 +74,12 @@ class DecodeStateOwn(DecodeState):
     _fields_ = [("own_past", i32), ("own_lo", vp)]
 
 
+class DecodeStateRagged(DecodeStateOwn):
+    """DecodeStateOwn followed by the ragged regime's three fields (continuous batching).  The library reads them only when `flags`
+    has DECODE_RAGGED, so every other caller may keep passing a DecodeStateOwn."""
+    _fields_ = [("row_base", vp), ("kstage", vp), ("vstage", vp)]
+
+
 class LogprobOpts(C.Structure):
     _fields_ = [("n", i32), ("chosen_lp", vp), ("chosen_rank", vp), ("top_ids", vp), ("top_lp", vp)]
 
@@ -143,6 +149,7 @@ SIGNATURES = {
     "o3v_gemm_bf16_splitk": [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, sz, vp],
     "o3v_resize_bicubic_aa": [vp, i32, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, i32, vp],
     "o3v_crop_resize_bilinear": [vp, vp, vp, i32, i32, i32, i32, vp],
+    "o3v_attn_decode_ragged": [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, vp],
     "o3v_attn_decode_group": [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, f32, vp],
     "o3v_decode_sync_bytes": [],
     "o3v_decode_attn_block_capacity": [i32, i32],
@@ -218,6 +225,7 @@ LOGPROB_ROW_SCRATCH_FLOATS = 384  # O3V_LOGPROB_ROW_SCRATCH_FLOATS
 # o3v_decode_state.flags: O3V_DECODE_LAYER_BLOCK, O3V_DECODE_NO_TAIL_NORM, O3V_DECODE_NO_QKV_FUSED_NORM (these two switch a form OFF),
 # O3V_DECODE_KV8_EMULATE (tests: the fp8 K/V arithmetic on a bf16 cache)
 DECODE_LAYER_BLOCK, DECODE_NO_TAIL_NORM, DECODE_NO_QKV_FUSED_NORM, DECODE_KV8_EMULATE = 1, 2, 4, 8
+DECODE_RAGGED = 16              # O3V_DECODE_RAGGED: the state is a DecodeStateRagged
 
 _lib = None
 

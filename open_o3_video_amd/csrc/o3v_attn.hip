@@ -324,14 +324,15 @@ __global__ __launch_bounds__(256, 2) void attn_tiles_kernel(const bf16_t* __rest
 // softmax stream; streams are merged at the end, splits by o3v_attn_decode_combine.
 // ------------------------------------------------------------------------------------------------
 
+// The scalar form's work of one workgroup (split, hk, b) of a row whose context is ctx: shared by attn_decode_kernel (one ctx for
+// every row) and attn_decode_ragged_kernel (ctx per row), so a row's bits do not depend on which of them ran it.
 template <int D>
-__global__ __launch_bounds__(256) void attn_decode_kernel(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ Kc,
-                                                          const bf16_t* __restrict__ Vc, float* __restrict__ part_o,
-                                                          float* __restrict__ part_ml, const int* __restrict__ k_lo_arr,
-                                                          int ctx, int Hq, int Hkv, int n_rep, long k_hs, long k_bs,
-                                                          float scale_log2e) {
+__device__ __forceinline__ void attn_decode_scalar_body(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ Kc,
+                                                        const bf16_t* __restrict__ Vc, float* __restrict__ part_o,
+                                                        float* __restrict__ part_ml, const int* __restrict__ k_lo_arr, int ctx,
+                                                        int Hq, int Hkv, int n_rep, long k_hs, long k_bs, float scale_log2e,
+                                                        const int split, const int nsplit, const int hk, const int b) {
     constexpr int LPK = D / 8, KPW = 64 / LPK;
-    const int split = blockIdx.x, nsplit = gridDim.x, hk = blockIdx.y, b = blockIdx.z;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int slot = lane / LPK, part = lane % LPK;
     const int k_lo = k_lo_arr ? k_lo_arr[b] : 0;
@@ -466,6 +467,16 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const bf16_t* __restri
     }
 }
 
+template <int D>
+__global__ __launch_bounds__(256) void attn_decode_kernel(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ Kc,
+                                                          const bf16_t* __restrict__ Vc, float* __restrict__ part_o,
+                                                          float* __restrict__ part_ml, const int* __restrict__ k_lo_arr,
+                                                          int ctx, int Hq, int Hkv, int n_rep, long k_hs, long k_bs,
+                                                          float scale_log2e) {
+    attn_decode_scalar_body<D>(Q, Kc, Vc, part_o, part_ml, k_lo_arr, ctx, Hq, Hkv, n_rep, k_hs, k_bs, scale_log2e, blockIdx.x,
+                               gridDim.x, blockIdx.y, blockIdx.z);
+}
+
 // Decode attention on the matrix cores: attn_decode_mfma_body in o3v_attn_decode_body.h (shared with o3v_fused.hip)
 __global__ __launch_bounds__(256) void attn_decode_mfma_kernel(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ Kc,
                                                                const bf16_t* __restrict__ Vc, float* __restrict__ part_o,
@@ -488,6 +499,104 @@ __global__ __launch_bounds__(256) void attn_decode_mfma_gap_kernel(const bf16_t*
     attn_decode_mfma_body<false, true>(Q, Kc, Vc, part_o, part_ml, k_lo_arr, ctx, Hq, Hkv, n_rep, k_hs, k_bs, scale_log2e, kbeg,
                                        nsplit_tot, split_off, G, P, blockIdx.x, gridDim.x, blockIdx.y, blockIdx.z, smem, AttnHandoff{},
                                        pf, own_lo_arr);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Ragged decode attention (continuous batching): every row has its own context, ctx_b = row_base[b] + step + 1, and its cache
+// starts at slot 0.  A LIVE row (1 <= ctx_b <= Tmax) first appends the new token's K/V -- the staging rows Knew / Vnew
+// [B][Hkv][D] that q/k/v wrote -- to slot ctx_b - 1 with plain vector stores: exactly one wave per (b, kv head), the one whose
+// key range holds that slot.  A workgroup barrier orders the stores before the workgroup's own loads; no other workgroup reads
+// the slot in this launch.  Then the workgroup runs the body of the kernels above on ITS ctx_b, so the splits are cut from the
+// row's own context and the row's bits are those of o3v_attn_decode on that row alone.
+// Reads and masks: keys >= ctx_b are clamped onto slot ctx_b - 1 by the bodies (and masked), so nothing at or behind ctx_b is
+// read, and slot ctx_b - 1 is read only after it has been overwritten: stale bytes there, NaN included, never reach a sum.  In
+// the matrix-core form only the appending wave's last tile reaches slot ctx_b - 1; in the scalar form the other waves of the
+// appending workgroup may clamp onto it too, behind the barrier.
+// An IDLE row (any other ctx_b: retired, empty, past its capacity) touches none of its cache: its workgroups publish the neutral
+// partial (m, l) = (-1e30, 0), o = 0 over whatever part_o / part_ml held, and attn_decode_combine_kernel turns that into +0.
+// ------------------------------------------------------------------------------------------------
+template <int D>
+__device__ __forceinline__ void ragged_idle_partials(float* __restrict__ part_o, float* __restrict__ part_ml, int Hq, int n_rep,
+                                                     int split, int nsplit, int hk, int b) {
+    for (int i = threadIdx.x; i < n_rep * D; i += 256) {
+        const int r = i / D, d = i % D;
+        const size_t idx = (((size_t)b * Hq + hk * n_rep + r) * nsplit + split);
+        part_o[idx * D + d] = 0.f;
+        if (d == 0) {
+            part_ml[idx * 2] = -1e30f;
+            part_ml[idx * 2 + 1] = 0.f;
+        }
+    }
+}
+// one wave: lanes 0 .. D/8-1 store K's 16-byte chunks of the new row, the next D/8 lanes V's
+template <int D>
+__device__ __forceinline__ void ragged_append(bf16_t* Krow, bf16_t* Vrow, const bf16_t* __restrict__ Knew,
+                                              const bf16_t* __restrict__ Vnew, int lane) {
+    constexpr int LPK = D / 8;
+    if (lane < 2 * LPK) {
+        const bool isv = lane >= LPK;
+        const int c = isv ? lane - LPK : lane;
+        *reinterpret_cast<u32x4*>((isv ? Vrow : Krow) + c * 8) = *reinterpret_cast<const u32x4*>((isv ? Vnew : Knew) + c * 8);
+    }
+}
+// row b's context, or 0 for an idle row (64-bit: a retired row's base is a large negative number)
+__device__ __forceinline__ int ragged_ctx(const int* __restrict__ row_base, int b, int step, int Tmax) {
+    const long c = (long)row_base[b] + step + 1;
+    return c >= 1 && c <= Tmax ? (int)c : 0;
+}
+
+template <int D>
+__global__ __launch_bounds__(256) void attn_decode_ragged_kernel(const bf16_t* __restrict__ Q, bf16_t* Kc, bf16_t* Vc,
+                                                                 const bf16_t* __restrict__ Knew, const bf16_t* __restrict__ Vnew,
+                                                                 float* __restrict__ part_o, float* __restrict__ part_ml,
+                                                                 const int* __restrict__ row_base, int step, int Hq, int Hkv,
+                                                                 int n_rep, int Tmax, float scale_log2e) {
+    constexpr int LPK = D / 8, KPW = 64 / LPK;
+    const int split = blockIdx.x, nsplit = gridDim.x, hk = blockIdx.y, b = blockIdx.z;
+    const int ctx = ragged_ctx(row_base, b, step, Tmax);  // workgroup-uniform
+    if (ctx == 0) {
+        ragged_idle_partials<D>(part_o, part_ml, Hq, n_rep, split, nsplit, hk, b);
+        return;
+    }
+    const long k_hs = (long)Tmax * D, k_bs = (long)Hkv * Tmax * D;
+    // the body's split arithmetic: key k of the split belongs to wave ((k - k0) / KPW) % 4
+    int chunk = (ctx + nsplit - 1) / nsplit;
+    chunk = (chunk + 16 * KPW - 1) / (16 * KPW) * (16 * KPW);
+    const int k0 = split * chunk, last = ctx - 1;
+    if (k0 <= last && last < k0 + chunk && (int)(threadIdx.x >> 6) == (((last - k0) / KPW) & 3)) {
+        const size_t row = (size_t)b * k_bs + (size_t)hk * k_hs + (size_t)last * D, st = ((size_t)b * Hkv + hk) * D;
+        ragged_append<D>(Kc + row, Vc + row, Knew + st, Vnew + st, threadIdx.x & 63);
+    }
+    __syncthreads();
+    attn_decode_scalar_body<D>(Q, Kc, Vc, part_o, part_ml, nullptr, ctx, Hq, Hkv, n_rep, k_hs, k_bs, scale_log2e, split, nsplit, hk, b);
+}
+
+__global__ __launch_bounds__(256) void attn_decode_ragged_mfma_kernel(const bf16_t* __restrict__ Q, bf16_t* Kc, bf16_t* Vc,
+                                                                      const bf16_t* __restrict__ Knew,
+                                                                      const bf16_t* __restrict__ Vnew, float* __restrict__ part_o,
+                                                                      float* __restrict__ part_ml, const int* __restrict__ row_base,
+                                                                      int step, int Hq, int Hkv, int n_rep, int Tmax,
+                                                                      float scale_log2e) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];  // 4 x V slice, reused for the merge
+    constexpr int D = 128, KT = 32;
+    const int split = blockIdx.x, nsplit = gridDim.x, hk = blockIdx.y, b = blockIdx.z;
+    const int ctx = ragged_ctx(row_base, b, step, Tmax);  // workgroup-uniform
+    if (ctx == 0) {
+        ragged_idle_partials<D>(part_o, part_ml, Hq, n_rep, split, nsplit, hk, b);
+        return;
+    }
+    const long k_hs = (long)Tmax * D, k_bs = (long)Hkv * Tmax * D;
+    // the body's split arithmetic (kbeg = 0): wave w of the split owns keys [kw0, kw0 + per_wave)
+    int chunk = (ctx + nsplit - 1) / nsplit;
+    chunk = (chunk + 4 * KT - 1) / (4 * KT) * (4 * KT);
+    const int per_wave = chunk >> 2, kw0 = split * chunk + (int)(threadIdx.x >> 6) * per_wave, last = ctx - 1;
+    if (kw0 <= last && last < kw0 + per_wave) {
+        const size_t row = (size_t)b * k_bs + (size_t)hk * k_hs + (size_t)last * D, st = ((size_t)b * Hkv + hk) * D;
+        ragged_append<D>(Kc + row, Vc + row, Knew + st, Vnew + st, threadIdx.x & 63);
+    }
+    __syncthreads();
+    attn_decode_mfma_body<false>(Q, Kc, Vc, part_o, part_ml, nullptr, ctx, Hq, Hkv, n_rep, k_hs, k_bs, scale_log2e, 0, nsplit, 0, 1, 0,
+                                 split, nsplit, hk, b, smem, AttnHandoff{});
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -831,6 +940,41 @@ extern "C" int o3v_attn_decode(const void* Q, const void* Kc, const void* Vc, vo
         default: return O3V_ERR_SHAPE;
     }
 #undef O3V_AD
+    O3V_CHECK_LAUNCH();
+    return O3V_OK;
+}
+
+// Per-row contexts (see attn_decode_ragged_kernel): nsplit > 0 at D == 128 is the matrix-core form, nsplit < 0 (and every other D)
+// the scalar form, as in o3v_attn_decode.
+extern "C" int o3v_attn_decode_ragged(const void* Q, void* Kc, void* Vc, const void* Knew, const void* Vnew, void* out, float* part_o,
+                                      float* part_ml, const int* row_base, int step, int B, int Hq, int Hkv, int D, int Tmax,
+                                      int nsplit, float scale, hipStream_t stream) {
+    if (!Q || !Kc || !Vc || !Knew || !Vnew || !out || !part_o || !part_ml || !row_base || step < 0 || B < 0 || Hq <= 0 || Hkv <= 0 ||
+        (Hq % Hkv) || Tmax <= 0 || nsplit == 0 || nsplit > 64 || nsplit < -64)
+        return O3V_ERR_ARG;
+    const int n_rep = Hq / Hkv;
+    if (n_rep > NREP_MAX || (D != 32 && D != 64 && D != 128)) return O3V_ERR_SHAPE;
+    if (B == 0) return O3V_OK;
+    const float sl2 = scale * 1.4426950408889634f;
+    const bool use_valu = nsplit < 0 || D != 128;
+    if (nsplit < 0) nsplit = -nsplit;
+    dim3 grid(nsplit, Hkv, B), block(256);
+#define O3V_AR(DD)                                                                                                              \
+    O3V_KLAUNCH((attn_decode_ragged_kernel<DD>), grid, block, 0, stream, (const bf16_t*)Q, (bf16_t*)Kc, (bf16_t*)Vc,            \
+                (const bf16_t*)Knew, (const bf16_t*)Vnew, part_o, part_ml, row_base, step, Hq, Hkv, n_rep, Tmax, sl2);          \
+    O3V_KLAUNCH((attn_decode_combine_kernel<DD>), dim3(B* Hq), dim3(128), 0, stream, part_o, part_ml, (bf16_t*)out, nsplit)
+    if (D == 32) {
+        O3V_AR(32);
+    } else if (D == 64) {
+        O3V_AR(64);
+    } else if (use_valu) {
+        O3V_AR(128);
+    } else {
+        O3V_KLAUNCH(attn_decode_ragged_mfma_kernel, grid, block, 4 * 32 * 288, stream, (const bf16_t*)Q, (bf16_t*)Kc, (bf16_t*)Vc,
+                    (const bf16_t*)Knew, (const bf16_t*)Vnew, part_o, part_ml, row_base, step, Hq, Hkv, n_rep, Tmax, sl2);
+        O3V_KLAUNCH((attn_decode_combine_kernel<128>), dim3(B * Hq), dim3(128), 0, stream, part_o, part_ml, (bf16_t*)out, nsplit);
+    }
+#undef O3V_AR
     O3V_CHECK_LAUNCH();
     return O3V_OK;
 }

@@ -454,6 +454,7 @@ struct Regime {
     Weights weights, qkv_weights, mlp_weights;        // of the linears; of q/k/v; of gate/up and down_proj
     bool norm_apart, qkv_fused_norm, qk_norm, group;  // fixed for the call
     bool kv8, kv8_emulate;                            // fp8 K/V cache; its arithmetic emulated on a bf16 cache (tests)
+    bool ragged;                                      // a context per row (row_base): staging rows, o3v_attn_decode_ragged
     const int* own_lo;                                // group rows with left-padded suffixes in their own caches: the gap mask, else NULL
     bool block, layer_block, tail;                    // tried, may fall back: see settle()
 };
@@ -508,6 +509,10 @@ Regime decide_regime(const o3v_llm_desc* d, const o3v_decode_state* st) {
     r.kv8 = st->k8 != nullptr;
     r.kv8_emulate = !r.kv8 && (st->flags & O3V_DECODE_KV8_EMULATE);
     if (r.kv8 || r.kv8_emulate) r.block = r.layer_block = false;
+    // ragged rows (continuous batching; the three fields exist only behind O3V_DECODE_RAGGED): q/k/v writes the staging rows as under
+    // kv8, the attention kernel appends them at each row's own slot -- stand-alone launches
+    r.ragged = (st->flags & O3V_DECODE_RAGGED) && st->row_base != nullptr;
+    if (r.ragged) r.block = r.layer_block = false;
     // suffixes behind a shared prefix (o3v_llm_decode_ex has checked that this is a group on a prompt entry): the group kernels mask
     // each row's padding slots; NULL launches the kernels of before
     r.own_lo = r.group ? st->own_lo : nullptr;
@@ -534,10 +539,11 @@ struct Decode {
     bool normed_ready;  // w.normed holds RMSNorm(x; final_norm)
     void x_changed() { h_ready = h2_ready = normed_ready = false; }
     // where q/k/v appends the new token's K/V: slot slot0 + step of layer l's cache; fp8 K/V: the staging rows [B][Hkv][1][D]
-    char* kc(int l) const { return (char*)st->kcache + (r.kv8 ? 0 : l * layer_stride); }
-    char* vc(int l) const { return (char*)st->vcache + (r.kv8 ? 0 : l * layer_stride); }
-    int kv_slot() const { return r.kv8 ? 0 : slot0 + step; }
-    int kv_cap() const { return r.kv8 ? 1 : st->Tmax; }
+    // ragged rows: the staging rows kstage / vstage likewise
+    char* kc(int l) const { return r.ragged ? (char*)st->kstage : (char*)st->kcache + (r.kv8 ? 0 : l * layer_stride); }
+    char* vc(int l) const { return r.ragged ? (char*)st->vstage : (char*)st->vcache + (r.kv8 ? 0 : l * layer_stride); }
+    int kv_slot() const { return r.kv8 || r.ragged ? 0 : slot0 + step; }
+    int kv_cap() const { return r.kv8 || r.ragged ? 1 : st->Tmax; }
     uint32_t epoch(int l) const { return (uint32_t)(step * d->layers + l + 1); }  // of the one-launch forms
     bool first(int l) const { return l == 0 && step == step0; }                   // the launch at which settle() may switch a form off
     int sample(const o3v_logprob_opts* lp, const o3v_sampling_opts* so, const o3v_guided_opts* go) {
@@ -603,6 +609,10 @@ struct Decode {
     }
     // attention + merge of layer l on the stand-alone kernels
     int attention(int l) {
+        if (r.ragged)
+            return o3v_attn_decode_ragged(w.q, (char*)st->kcache + l * layer_stride, (char*)st->vcache + l * layer_stride, st->kstage,
+                                          st->vstage, w.att, st->part_o, st->part_ml, st->row_base, step, B, Hq, Hkv, D, st->Tmax,
+                                          st->nsplit, scale, s);
         if (r.kv8) {
             const size_t rows = (size_t)l * B * Hkv * st->Tmax;  // (token, kv head) rows of the layers before l
             return o3v_attn_decode_kv8(w.q, (char*)st->k8 + rows * D, (char*)st->v8 + rows * D, st->k8s + rows, st->v8s + rows, st->kcache,
@@ -718,8 +728,12 @@ extern "C" int o3v_llm_decode_guided(const o3v_llm_desc* d, const o3v_decode_sta
     const int B = st->B;
     // shared prompt entries: the caches hold only the generated tokens (slot = step), the prompt K/V live once per prompt
     const bool pfx = st->kprefix != nullptr;
+    const bool ragged = (st->flags & O3V_DECODE_RAGGED) && st->row_base != nullptr;  // rows guard their own capacity
     if (B <= 0 || B > 32 || step0 < 0 || n_steps < 0 || step0 + n_steps > st->Tnew ||
-        (pfx ? st->own_past + st->Tnew : st->S + st->Tnew) > st->Tmax + 1)
+        (!ragged && (pfx ? st->own_past + st->Tnew : st->S + st->Tnew) > st->Tmax + 1))
+        return O3V_ERR_ARG;
+    if (ragged && (st->group > 1 || pfx || st->k8 || st->own_past || st->own_lo || (st->flags & O3V_DECODE_KV8_EMULATE) || !st->kstage ||
+                   !st->vstage || st->Tmax <= 0))
         return O3V_ERR_ARG;
     // suffixes behind a shared prefix: a group on a prompt entry, bf16 K/V
     if ((st->own_past || st->own_lo) && (st->own_past < 0 || !pfx || st->group <= 1 || st->k8)) return O3V_ERR_ARG;
@@ -739,7 +753,7 @@ extern "C" int o3v_llm_decode_guided(const o3v_llm_desc* d, const o3v_decode_sta
         c.step = step0 + i;
         TRY(c.sample(lp, so, go));
         if (skip_last_forward && i == n_steps - 1) break;
-        if (c.slot0 + c.step >= st->Tmax) return O3V_ERR_ARG;
+        if (!ragged && c.slot0 + c.step >= st->Tmax) return O3V_ERR_ARG;
         // one decode forward: token `step` sits in cache slot S+step, context = S+step+1 keys
         if (st->do_sample) TRY(o3v_embed_tokens(d->embed, st->cur_tok, st->x, B, c.H, s));
         c.x_changed();  // x is the sampler's embedding row

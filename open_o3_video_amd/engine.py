@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from . import _lib, guided, indexing
+from .continuous import IDLE_BASE, ContinuousScheduler, default_session_columns
 from .config import O3VConfig
 from .weights import DeviceWeights
 
@@ -182,13 +183,37 @@ class GenerateOutput:
     prompt_logprobs: Optional[Logprobs] = None
 
 
+@dataclass
+class ContinuousRequest:
+    """One request of O3VEngine.generate_continuous: the prompt, its precomputed visual inputs (as generate takes them) and its
+    own completion length."""
+    ids: object                               # 1-D token ids
+    max_new_tokens: int = 16
+    vis_embeds: Optional[torch.Tensor] = None
+    image_grid_thw: object = None
+    video_grid_thw: object = None
+    second_per_grid_ts: object = None
+
+
+@dataclass
+class ContinuousOutput:
+    tokens: torch.Tensor                      # i64 [n] (host): the generated tokens, trimmed as generate trims a row (first EOS kept)
+    margins: Optional[torch.Tensor]           # f32 [n] top1-top2 margins of those tokens
+    row: int                                  # where it ran: decode row, first column, session (1-based)
+    t0: int
+    session: int
+    timings: dict                             # of the whole call; filled when it returns
+    sequences: torch.Tensor                   # i64 [1, S + n] (host): prompt + tokens
+
+
 class _DecodeBuffers:
     """The device state of one generate call's decode: every tensor whose address goes into o3v_decode_state / o3v_sampling_opts /
     o3v_logprob_opts, the structs themselves (st; so / lp_opts: None when the call does not use them) and the host_stats array.
     The structs hold bare addresses, so this object lives until the last o3v_llm_decode_ex call and the final check_waits()."""
 
     def __init__(self, eng: "O3VEngine", plan: DecodePlan, S, T, G, ids_rep, pad_rep, eos_token_ids, row_ids, return_margins, n_lp,
-                 sampling, knobs, cosd, sind, logits, kc, vc, kc0, vc0, kv8=None, kv8_emulate=False, own=None, guide=None):
+                 sampling, knobs, cosd, sind, logits, kc, vc, kc0, vc0, kv8=None, kv8_emulate=False, own=None, guide=None,
+                 ragged=None):
         tc, dev = eng.cfg.text, eng.dev
         B, V = plan.B, tc.vocab_size
         zeros = lambda shape, dtype: torch.zeros(shape, dtype=dtype, device=dev)
@@ -244,15 +269,18 @@ class _DecodeBuffers:
             if getattr(eng, "_debug_poison_sync", False):     # test hook: tickets that can never reach "last" -> the waits give up
                 self.sync[:1024].view(torch.int32).fill_(0x40000000)
         shared = plan.shared_prompt
-        self.st = _lib.DecodeStateOwn(B=B, S=S, Tmax=plan.Tmax, Tnew=T, nsplit=plan.nsplit, x=self.x.data_ptr(), kcache=kc.data_ptr(),
-                                      vcache=vc.data_ptr(), cosT=cosd.data_ptr(), sinT=sind.data_ptr(), logits=logits.data_ptr(),
-                                      seen=self.seen.data_ptr(), cur_tok=self.cur_tok.data_ptr(), finished=self.finished.data_ptr(),
-                                      out_ids=self.out_ids.data_ptr(), margins=addr(self.margins), eos_ids=self.eos.data_ptr(),
-                                      k_lo=self.k_lo.data_ptr(), row_id=self.rid.data_ptr(), part_o=self.part_o.data_ptr(),
-                                      part_ml=self.part_ml.data_ptr(), sample_scratch=self.scratch.data_ptr(),
-                                      workspace=self.ws.data_ptr(), ws_bytes=nbytes, group=plan.group, sync=addr(self.sync),
-                                      kprefix=kc0.data_ptr() if shared else 0, vprefix=vc0.data_ptr() if shared else 0,
-                                      prefix_cap=int(kc0.shape[3]) if shared else 0, rows_per_prompt=G if shared else 0, **knobs)
+        # ragged = row_base i32 [B] (or a list to upload): every row has its own context row_base[b] + step + 1 (continuous batching);
+        # q/k/v then writes the new token's K/V into staging rows and the attention kernel appends them at the row's own slot
+        state_type = _lib.DecodeStateOwn if ragged is None else _lib.DecodeStateRagged
+        self.st = state_type(B=B, S=S, Tmax=plan.Tmax, Tnew=T, nsplit=plan.nsplit, x=self.x.data_ptr(), kcache=kc.data_ptr(),
+                             vcache=vc.data_ptr(), cosT=cosd.data_ptr(), sinT=sind.data_ptr(), logits=logits.data_ptr(),
+                             seen=self.seen.data_ptr(), cur_tok=self.cur_tok.data_ptr(), finished=self.finished.data_ptr(),
+                             out_ids=self.out_ids.data_ptr(), margins=addr(self.margins), eos_ids=self.eos.data_ptr(),
+                             k_lo=self.k_lo.data_ptr(), row_id=self.rid.data_ptr(), part_o=self.part_o.data_ptr(),
+                             part_ml=self.part_ml.data_ptr(), sample_scratch=self.scratch.data_ptr(),
+                             workspace=self.ws.data_ptr(), ws_bytes=nbytes, group=plan.group, sync=addr(self.sync),
+                             kprefix=kc0.data_ptr() if shared else 0, vprefix=vc0.data_ptr() if shared else 0,
+                             prefix_cap=int(kc0.shape[3]) if shared else 0, rows_per_prompt=G if shared else 0, **knobs)
         self.own_lo = None
         if own is not None:
             self.own_lo = torch.from_numpy(np.ascontiguousarray(own[1], dtype=np.int32)).to(dev)
@@ -264,6 +292,12 @@ class _DecodeBuffers:
                          (0 if eng.qkv_fused_norm else _lib.DECODE_NO_QKV_FUSED_NORM) | (_lib.DECODE_KV8_EMULATE if kv8_emulate else 0))
         if kv8 is not None:
             self.st.k8, self.st.v8, self.st.k8s, self.st.v8s = (t.data_ptr() for t in kv8)
+        self.row_base = self.stage = None
+        if ragged is not None:
+            self.row_base = torch.as_tensor(ragged, dtype=torch.int32).to(dev)
+            self.stage = tuple(empty((B, tc.num_key_value_heads, 1, tc.head_dim), torch.bfloat16) for _ in range(2))
+            self.st.row_base, self.st.kstage, self.st.vstage = self.row_base.data_ptr(), *(t.data_ptr() for t in self.stage)
+            self.st.flags |= _lib.DECODE_RAGGED
 
     def check_waits(self):
         """Reads the sticky time-out word of the in-launch waits (a device-to-host copy); raises if one of them gave up."""
@@ -729,6 +763,13 @@ class O3VEngine:
         kv_dtype = "bf16" if emulate else kv_cache_in_effect(self.kv_cache_dtype, tc.head_dim, plan)
         if kv_dtype == "fp8" or emulate:
             plan = make_plan(False)
+        # test hook: the rows decode through the ragged state (row_base = S for every row) -- the kernels of generate_continuous on
+        # the inputs of an ordinary call, whose outputs they must reproduce bit for bit
+        debug_ragged = bool(getattr(self, "_debug_ragged", False))
+        if debug_ragged:
+            if P or G != 1 or kv_dtype != "bf16" or emulate or pad.any() or n_lp or sampling or guide is not None or do_sample:
+                raise ValueError("_debug_ragged: unpadded prompts of equal length, one greedy completion each, bf16 K/V, no extras")
+            plan = make_plan(False)
         B = plan.B
         tm = {}
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)] if sync_timings else None
@@ -786,7 +827,8 @@ class O3VEngine:
         knobs = dict(pad_id=pad_id, n_eos=len(eos_token_ids), do_sample=int(do_sample), rep_penalty=float(repetition_penalty),
                      temperature=float(temperature), top_p=float(top_p), seed=int(seed) & (2 ** 64 - 1), top_k=max(0, int(top_k or 0)))
         buf = _DecodeBuffers(self, plan, state["S"], T, state["G"], ids_rep, state["pad_rep"], eos_token_ids, row_ids, return_margins,
-                             n_lp, sampling, knobs, cosd, sind, logits, kc, vc, kc0, vc0, kv8, emulate, own=state["own"], guide=guide)
+                             n_lp, sampling, knobs, cosd, sind, logits, kc, vc, kc0, vc0, kv8, emulate, own=state["own"], guide=guide,
+                             ragged=[S] * B if debug_ragged else None)
         tm["kv_cache_dtype"] = kv_dtype
         tm["mlp_weights"] = mlp_weights_in_effect(self.w.t, plan)
         tm["kv_cache_bytes"] = int((kc.numel() + vc.numel() + (kc0.numel() + vc0.numel() if plan.shared_prompt else 0)) * 2 +
@@ -821,6 +863,119 @@ class O3VEngine:
             lp = Logprobs(lp.token[:, :done], lp.rank[:, :done], lp.top_ids[:, :done], lp.top[:, :done])
         return GenerateOutput(sequences=seqs, margins=None if margins is None else margins[:, :done], n_steps=done,
                               timings=tm, logprobs=lp, prompt_logprobs=plp)
+
+    # ------------------------------------------------------------------------------------------ continuous batching
+    @torch.no_grad()
+    def generate_continuous(self, requests, rows: int, eos_token_ids: Sequence[int] = (), repetition_penalty: float = 1.0,
+                            pad_token_id: Optional[int] = None, steps_per_sync: int = 16, session_columns: Optional[int] = None,
+                            return_margins: bool = True, prefix_keys=None):
+        """Greedy decoding of a list of requests over `rows` decode rows that are refilled in flight: a row whose request has ended
+        takes the next request at the following chunk boundary instead of decoding pad tokens until the longest row of its batch
+        ends ("Ragged rows").  -> one ContinuousOutput per request, in request order.
+
+        A request is a ContinuousRequest (or a dict of its fields): 1-D `ids`, `max_new_tokens`, and its visual inputs as generate
+        takes them precomputed (`vis_embeds`, `image_grid_thw`, `video_grid_thw`, `second_per_grid_ts`).  `prefix_keys`: None or one
+        `prefix_key` per request (generate's prompt K/V reuse; every request is prefilled alone, so it applies to each).
+
+        State: one set of decode buffers with B = rows; caches [layers][rows][Hkv][Tmax][D] with Tmax = max(len(ids) + max_new) +
+        steps_per_sync (a row runs on to the end of the chunk in which it ends); ids, margins and the M-RoPE table hold
+        `session_columns` columns (default: continuous.default_session_columns).  A request is admitted into a free row at a chunk
+        boundary, column t0, if t0 + max_new <= session_columns: its prompt is prefilled alone, its K/V copied to slots [0, S) of the
+        row, and row_base[row] = S - t0 tells the kernels where the row's context ends.  When the next request does not fit, the
+        live rows drain and a new session starts at column 0 on the same buffers.  All of it is enqueued on the current stream.
+
+        Rows never depend on one another: with rows, steps_per_sync and the weights fixed, a request's tokens and margins are the
+        same bits whichever row it lands in and whenever it is admitted.  Sampling, log-probs, the extended controls, guides, stop
+        strings, fp8 K/V and shared-prefix groups are indexed by the decode column or need per-row kernels of their own: they
+        keep static batches (generate).  timings of the call: ContinuousOutput.timings (one dict, shared)."""
+        cfg, tc = self.cfg, self.cfg.text
+        rows = int(rows)
+        if not 1 <= rows <= self.MAX_ROWS:
+            raise ValueError(f"rows must be in 1..{self.MAX_ROWS}")
+        reqs = [r if isinstance(r, ContinuousRequest) else ContinuousRequest(**r) for r in requests]
+        if not reqs:
+            return []
+        keys = list(prefix_keys) if prefix_keys is not None else [None] * len(reqs)
+        if len(keys) != len(reqs):
+            raise ValueError("prefix_keys: one per request")
+        if self.kv_cache_dtype != "bf16":
+            raise ValueError("generate_continuous decodes on bf16 K/V (the fp8 K/V cache keeps static batches)")
+        ids_all = [np.asarray(r.ids.cpu() if torch.is_tensor(r.ids) else r.ids, dtype=np.int64).reshape(-1) for r in reqs]
+        if any(i.size == 0 for i in ids_all):
+            raise ValueError("empty prompt")
+        sync = max(1, int(steps_per_sync))
+        max_new = [int(r.max_new_tokens) for r in reqs]
+        columns = default_session_columns(max_new, sync) if session_columns is None else int(session_columns)
+        sched = ContinuousScheduler([i.size for i in ids_all], max_new, rows, columns, sync, eos_token_ids)
+        ctx_max = max(i.size + m for i, m in zip(ids_all, max_new))
+        Tmax = ctx_max + sync
+        # the context splits are a constant of the call (a request's bits depend on them): plan_decode's rule on the longest context
+        nsplit_env = os.environ.get("O3V_NSPLIT")
+        nsplit = int(nsplit_env) if nsplit_env else max(1, min(64, (ctx_max + 127) // 128, max(1, 640 // (rows * tc.num_key_value_heads))))
+        plan = DecodePlan(rows, 0, False, Tmax, nsplit, 0, False)
+        pad_id = cfg.pad_token_id if pad_token_id is None else int(pad_token_id)
+        dev, V, D = self.dev, tc.vocab_size, tc.head_dim
+        kc, vc = self.alloc_cache(rows, Tmax)
+        cosd = torch.zeros((rows, columns, D), dtype=torch.bfloat16, device=dev)
+        sind = torch.zeros_like(cosd)
+        logits = torch.zeros((rows, V), dtype=torch.bfloat16, device=dev)
+        knobs = dict(pad_id=pad_id, n_eos=len(eos_token_ids), do_sample=0, rep_penalty=float(repetition_penalty), temperature=1.0,
+                     top_p=1.0, seed=0, top_k=0)
+        buf = _DecodeBuffers(self, plan, 0, columns, 1, np.zeros((rows, 1), dtype=np.int64), np.zeros(rows, dtype=np.int64),
+                             eos_token_ids, None, return_margins, 0, None, dict(knobs, rep_penalty=1.0), cosd, sind, logits, kc, vc,
+                             None, None, ragged=[IDLE_BASE] * rows)
+        buf.st.rep_penalty = float(repetition_penalty)
+        buf.finished.fill_(1)
+        self._last_prompt = None
+        tm = {"prefix_tokens_reused": 0}
+        out = [None] * len(reqs)
+
+        def admit(a):
+            r, b = reqs[a.request], a.row
+            ids = ids_all[a.request][None]
+            S, T = ids.shape[1], max_new[a.request]
+            mask = np.ones_like(ids)
+            vis, grid, vgrid, n_img_rows = self._visual(None, r.image_grid_thw, None, r.vis_embeds, None, r.video_grid_thw, None)
+            pos, deltas = self._positions(ids, mask, grid, vgrid, r.second_per_grid_ts)
+            x, k1, v1, _, _, past, _ = self._prefill_prompt(ids, np.zeros(1, dtype=np.int64), pos, vis, n_img_rows, 1,
+                                                            DecodePlan(1, 0, False, S, 1, 0, False), keys[a.request])
+            tm["prefix_tokens_reused"] += int(past)
+            kc[:, b, :, :S].copy_(k1[:, 0])
+            vc[:, b, :, :S].copy_(v1[:, 0])
+            logits[b].copy_(self.head(x[-1:])[0])
+            cos, sin = self.mrope_table(indexing.decode_positions(mask, deltas, T).reshape(3, T))
+            cosd[b, a.t0:a.t0 + T].copy_(cos)
+            sind[b, a.t0:a.t0 + T].copy_(sin)
+            buf.seen[b].zero_()
+            if repetition_penalty != 1.0:
+                ids_dev = torch.from_numpy(ids.astype(np.int32)).to(dev)
+                _lib.call("o3v_mark_seen", _ptr(ids_dev), _ptr(buf.seen[b]), 1, S, V, _stream())
+            buf.finished[b] = 0
+            buf.row_base[b] = a.row_base
+
+        while not sched.done():
+            for a in sched.admit():
+                admit(a)
+            c = sched.chunk()
+            _lib.call("o3v_llm_decode_ex", C.byref(self.w.llm), C.byref(buf.st), None, None, c.step0, c.n_steps, int(c.skip_last_forward),
+                      _stream())
+            # the one device-to-host copy of the chunk: what its columns hold
+            got = buf.out_ids[:, c.step0:c.step0 + c.n_steps].cpu().numpy()
+            session = sched.sessions
+            for r in sched.retire(got):
+                buf.finished[r.row] = 1
+                buf.row_base[r.row] = IDLE_BASE
+                toks = torch.from_numpy(np.asarray(sched.row_toks[r.row][:r.n], dtype=np.int64))
+                margins = buf.margins[r.row, r.t0:r.t0 + r.n].clone() if return_margins else None
+                out[r.request] = ContinuousOutput(tokens=toks, margins=margins, row=r.row, t0=r.t0, session=session, timings=tm,
+                                                  sequences=torch.cat([torch.from_numpy(ids_all[r.request]), toks])[None])
+        stats = buf.host_stats
+        layers_run = stats[0] * tc.num_hidden_layers
+        tm.update(decode_forwards=int(stats[0]), rows_refilled=int(sched.rows_refilled), sessions=int(sched.sessions),
+                  launches_per_layer=(stats[1] / layers_run) if layers_run else None,
+                  kv_cache_bytes=int((kc.numel() + vc.numel()) * 2), standalone_attention_layers=int(stats[3]), nsplit=nsplit,
+                  session_columns=columns, Tmax=Tmax)
+        return out
 
     def _rope_kw(self, grid, vgrid, second_per_grid_ts):
         """indexing.rope_index's keywords for this model (as _positions passes them)."""

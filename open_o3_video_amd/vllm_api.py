@@ -151,6 +151,16 @@ class SamplingParams:
                 raise ValueError("bad_words cannot contain an empty string.")
 
 
+def continuous_eligible(sp: "SamplingParams", kv_cache_dtype: str = "bf16") -> bool:
+    """Whether requests under `sp` may run through O3VEngine.generate_continuous (LLM(continuous_batching=True)): greedy, one
+    completion each, nothing that is indexed by the decode column (log-probs, the extended controls, guides, stop strings) and
+    bf16 K/V.  Everything else keeps static batches."""
+    return bool(sp.temperature == 0.0 and sp.n == 1 and sp.logprobs is None and sp.prompt_logprobs is None and not sp.min_p
+                and not sp.presence_penalty and not sp.frequency_penalty and not sp.min_tokens and not sp.logit_bias
+                and sp.allowed_token_ids is None and not sp.bad_words and sp.guided_decoding is None and not sp.stop
+                and kv_cache_dtype == "bf16")
+
+
 class _IncrementalDetokenizer:
     """Text of a growing token list, one token at a time (the prefix / read offset scheme of vLLM's detokenize_incrementally and
     HF's TextStreamer: a token's text is what decoding adds behind the text of the tokens before it, held back while it ends in an
@@ -305,7 +315,8 @@ class LLM:
                  min_pixels: int = 56 * 56, max_pixels: int = 14 * 14 * 4 * 1280, device="cuda",
                  enable_prefix_caching: bool = True, quantization: Optional[str] = None, mm_processor_kwargs: Optional[dict] = None,
                  position_mode: str = "pinned", fp8_prefill: bool = False, kv_cache_dtype: str = "auto",
-                 share_video_prefix: bool = False, enable_lora: bool = False, max_lora_rank: int = 16, **_):
+                 share_video_prefix: bool = False, enable_lora: bool = False, max_lora_rank: int = 16,
+                 continuous_batching: bool = False, **_):
         # vLLM's keyword: "fp8" / "fp8_e4m3" keep the K/V cache of independent-row decodes as e4m3fn rows with one power-of-two scale
         # per (token, kv head) (O3VEngine.kv_cache_dtype; not vLLM's per-tensor k_scale / v_scale: parity unpinned against vLLM)
         kv_dtypes = {"auto": "bf16", "bfloat16": "bf16", "fp8": "fp8", "fp8_e4m3": "fp8"}
@@ -372,6 +383,11 @@ class LLM:
         # (O3VEngine.generate(shared_prefix_len=...)); counted in shared_prefix_calls / shared_prefix_rows
         self.share_video_prefix = bool(share_video_prefix)
         self.shared_prefix_calls = self.shared_prefix_rows = 0
+        # opt-in: a generate() call with more requests than decode rows refills a row as soon as its request ends
+        # (O3VEngine.generate_continuous) where continuous_eligible() allows; counted in continuous_sessions / rows_refilled /
+        # decode_forwards.  Off, or not eligible: static batches of max_num_seqs rows.
+        self.continuous_batching = bool(continuous_batching)
+        self.continuous_sessions = self.rows_refilled = self.decode_forwards = 0
         # guided decoding: the token-level automata of the last two (pattern, EOS ids) on the device, and the tokenizer's byte strings
         self._guides = {}
         self._token_bytes = None
@@ -849,6 +865,28 @@ class LLM:
                 for P, at in groups:
                     for c0 in range(0, len(at), rows_per_call):
                         run_rows(at[c0:c0 + rows_per_call], shared=(P, prepared[at[0]][4]))
+            if (self.continuous_batching and len(prepared) > rows_per_call and rest
+                    and continuous_eligible(sp, getattr(self.engine, "kv_cache_dtype", "bf16"))):
+                # rows refilled in flight: every request not taken by a shared-prefix group, in input order
+                creqs = [dict(ids=prepared[i][1], max_new_tokens=sp.max_tokens,
+                              vis_embeds=cat_visual([prepared[i][2]], prepared[i][5]), image_grid_thw=prepared[i][3],
+                              video_grid_thw=prepared[i][6], second_per_grid_ts=prepared[i][7]) for i in rest]
+                outs = self.engine.generate_continuous(
+                    creqs, rows_per_call, eos_token_ids=eos, repetition_penalty=sp.repetition_penalty,
+                    pad_token_id=self.cfg.pad_token_id, return_margins=False,
+                    prefix_keys=[prepared[i][4] for i in rest] if self.enable_prefix_caching else None)
+                tmc = outs[0].timings
+                self.continuous_sessions += int(tmc["sessions"])
+                self.rows_refilled += int(tmc["rows_refilled"])
+                self.decode_forwards += int(tmc["decode_forwards"])
+                self.prefix_tokens_reused += int(tmc.get("prefix_tokens_reused", 0))
+                for i, o in zip(rest, outs):
+                    p = prepared[i]
+                    ro = RequestOutput(request_id=str(base + positions[i]), prompt=p[0], prompt_token_ids=p[1])
+                    finish(ro, 0, o.sequences[0], len(p[1]))
+                    results[i] = ro
+                    self._req += 1
+                return results
             for c0 in range(0, len(rest), rows_per_call):
                 run_rows(rest[c0:c0 + rows_per_call])
             return results
