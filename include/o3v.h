@@ -156,17 +156,6 @@ int o3v_gemv_norm_qkv_rope(const void* X, const void* norm_w, float eps, const v
 int o3v_linear_decode(const void* X, const void* norm_w, float eps, const void* W, const void* Wp, const void* bias,
                       const void* res, void* out, int M, int N, int K, int ldx, int ldo, int ldr, int epilogue,
                       o3v_stream_t stream);
-/* The residual linears of a batched decode layer (o_proj, down_proj; TF:692-757 `hidden = residual + ...` followed by the next
- * RMSNorm, TF:65-79) with the NEXT norm folded in: out = X . W^T + res and h = RMSNorm(out; next_norm_w) in ONE launch, 8 <= M <= 32
- * rows of already normalised X, Wp the fragment-major image, N <= 4096.  The waves that draw the last M tickets of the launch
- * normalise one row each once every part of `out` is in memory; h is bit-identical to o3v_rmsnorm(out, next_norm_w).  sync: the
- * zeroed buffer of o3v_decode_sync_bytes() (lines of its own; the sticky time-out word at O3V_SYNC_TMO_BYTE is shared), epoch = 1,
- * 2, ... counts the calls made on it.  The normalising waves read `out` and write h in 16-byte chunks: N % 16 == 0 and ldo, ldh
- * (and ldx) multiples of 8; ldr is any pitch.  O3V_ERR_SHAPE when the form does not apply (not gfx950, those alignments, fewer
- * than M storing waves -- there is one per 16 columns of N): issue o3v_linear_decode + o3v_rmsnorm instead. */
-int o3v_linear_decode_norm_next(const void* X, const void* Wp, const void* res, void* out, int M, int N, int K, int ldx, int ldo,
-                                int ldr, const void* next_norm_w, float eps, void* h, int ldh, uint32_t* sync, uint32_t epoch,
-                                o3v_stream_t stream);
 
 /* Decode linears on fp8 (OCP e4m3fn) weights, M <= 3 rows: W8 uint8 [N, K] (K % 16 == 0) with one fp32 scale per output
  * row; out = epi(scale[n] * (rmsnorm(X; norm_w) . fp8(W8[n])) + bias), x and the accumulation as in the bf16 path (the fp8
@@ -328,19 +317,6 @@ int o3v_gemm_fp8(const void* A8, const float* sa, const void* W8, const float* s
  * (o3v_gemm8p.hip's schedule; O3V_ERR_SHAPE where it does not apply).  Same bits either way. */
 int o3v_gemm_fp8_sched(const void* A8, const float* sa, const void* W8, const float* sw, const void* bias, const void* res, void* out,
                        int M, int N, int K, int lda, int ldw, int ldo, int ldr, int epilogue, int schedule, o3v_stream_t stream);
-
-/* The PERSISTENT layer block: RMSNorm + q/k/v (+bias, M-RoPE, cache append) -> attention -> merge -> o_proj + residual -> RMSNorm +
- * gate/up + SwiGLU of one decode layer at batch 1 as ONE launch (TF:692-757 up to the SwiGLU; down_proj + residual is the next
- * launch).  The grid is what the chip holds (three 256-thread workgroups per CU); every wave owns a static list of weight rows over
- * the three projections and keeps its next three rows in flight in registers -- also across the in-launch hand-offs, so ~60 MB of
- * o_proj / gate/up rows stream while the dependent attention chain runs.  act: bf16 [I] (input of down_proj).  Same arithmetic as
- * o3v_decode_attn_block + o3v_linear_decode(gate/up): bit-identical.  O3V_ERR_SHAPE unless head_dim 128, hidden == Hq*D a multiple of
- * 512 (2048, 3584) and the grid is resident: call the other entries instead.  sync: as o3v_decode_attn_block (its own ticket lines). */
-int o3v_decode_layer_block(void* x, const void* ln1, float eps, const void* qkv_w, const void* qkv_b, const void* o_w, const void* ln2,
-                           const void* gu_w, void* act, const void* cosT, const void* sinT, void* q_buf, void* att_buf, void* kcache,
-                           void* vcache, float* part_o, float* part_ml, const int* k_lo, int H, int I, int Hq, int Hkv, int D, int slot,
-                           int Tmax, int cs_stride_row, int cs_off, int nsplit, float scale, uint32_t* sync, uint32_t epoch,
-                           o3v_stream_t stream);
 
 /* o3v_decode_attn_block on fp8 (OCP e4m3fn) rows + per-row scales for the q/k/v and o projections (bit-identical to
  * o3v_gemv_norm_qkv_rope_fp8 + o3v_attn_decode + o3v_linear_decode_fp8) */
@@ -679,19 +655,18 @@ typedef struct {
     const int* row_base;
     void *kstage, *vstage;
 } o3v_decode_state;
-/* o3v_decode_state.flags.  LAYER_BLOCK: batch-1 bf16 decode may use the persistent layer block (o3v_decode_layer_block) where its
- * shapes allow, then one launch for the attention half + gate/up and one for down_proj per layer; otherwise o3v_decode_attn_block +
- * two launches.  NO_TAIL_NORM (inverted: set = off): at 8..32 bf16 rows with `sync` given, o_proj / down_proj do NOT normalise their
- * result for the linear that follows (o3v_linear_decode_norm_next); the norms are launches of their own.  NO_QKV_FUSED_NORM (inverted
- * as well): at 8 rows q/k/v does NOT take its RMSNorm fused; the norm is a launch of its own as at 9..32 rows.
+/* o3v_decode_state.flags: the bits below, or'ed; a zeroed word is the default decode.
+ * NO_QKV_FUSED_NORM (inverted: set = off; A/B): at 8 rows q/k/v does NOT take its RMSNorm fused; the norm is a launch of its own as
+ * at 9..32 rows.  Same bits either way.
  * KV8_EMULATE (tests; k8 == NULL, an ordinary bf16 cache): after q/k/v of every layer the new token's K/V rows are replaced by
  * dequant(quant(row)) (o3v_kv8_roundtrip, one more launch per layer) and the attention half runs on the stand-alone bf16 kernels:
- * the arithmetic of the fp8 K/V cache, bit for bit, on the bf16 kernels. */
-#define O3V_DECODE_LAYER_BLOCK 1
-#define O3V_DECODE_NO_TAIL_NORM 2
+ * the arithmetic of the fp8 K/V cache, bit for bit, on the bf16 kernels.
+ * RAGGED: the struct carries row_base / kstage / vstage behind own_lo (see there); without the bit they are not read.
+ * Values 1 and 2 are RETIRED: they selected two decode forms that were removed.  The library ignores them; they are not to be
+ * reused for anything else. */
 #define O3V_DECODE_NO_QKV_FUSED_NORM 4
 #define O3V_DECODE_KV8_EMULATE 8
-#define O3V_DECODE_RAGGED 16 /* the struct carries row_base / kstage / vstage behind own_lo */
+#define O3V_DECODE_RAGGED 16
 
 /* ---- opt-in fp8 K/V cache of the independent-row decode (vLLM kv_cache_dtype="fp8"; head_dim 128) --------------------------------
  * Storage: codes u8 [heads][Tmax][128] (OCP e4m3fn) + scales f32 [heads][Tmax], heads = (layers x) B x Hkv; 132 bytes per

@@ -166,8 +166,6 @@ SIGNATURES = {
     "o3v_rmsnorm_quantize_fp8": [vp, vp, vp, vp, i32, i32, i32, i32, f32, vp],
     "o3v_gemm_fp8": [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp],
     "o3v_gemm_fp8_sched": [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp],
-    "o3v_decode_layer_block": [vp, vp, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32,
-                               i32, i32, i32, f32, vp, C.c_uint32, vp],
     "o3v_sample_greedy": [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, i32, i32, vp, vp],
     "o3v_sample_greedy_embed": [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, i32, i32, vp, vp, vp, i32, vp],
     "o3v_gemv_norm_qkv_rope": [vp, vp, f32, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp],
@@ -179,7 +177,6 @@ SIGNATURES = {
     "o3v_linear_decode_mxfp4": [vp, vp, f32, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp],
     "o3v_linear_decode_mxfp4_rows": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp],
     "o3v_quantize_rows_mxfp4": [vp, vp, vp, i32, i32, i32, vp],
-    "o3v_linear_decode_norm_next": [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, f32, vp, i32, vp, C.c_uint32, vp],
     "o3v_gemv_norm_bf16": [vp, vp, f32, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp],
     "o3v_sample_top_p": [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, f32, f32, u64, vp, i32, i32, vp, vp],
     "o3v_sample_top_k_top_p": [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, f32, i32, f32, u64, vp, i32, i32, vp, vp],
@@ -222,9 +219,9 @@ SAMPLE_SCRATCH_FLOATS = 40960   # O3V_SAMPLE_SCRATCH_FLOATS in include/o3v.h
 MAX_LOGPROBS = 20               # O3V_MAX_LOGPROBS
 MAX_COUNT = 65535               # the u16 output counts of o3v_sampling_opts saturate here
 LOGPROB_ROW_SCRATCH_FLOATS = 384  # O3V_LOGPROB_ROW_SCRATCH_FLOATS
-# o3v_decode_state.flags: O3V_DECODE_LAYER_BLOCK, O3V_DECODE_NO_TAIL_NORM, O3V_DECODE_NO_QKV_FUSED_NORM (these two switch a form OFF),
-# O3V_DECODE_KV8_EMULATE (tests: the fp8 K/V arithmetic on a bf16 cache)
-DECODE_LAYER_BLOCK, DECODE_NO_TAIL_NORM, DECODE_NO_QKV_FUSED_NORM, DECODE_KV8_EMULATE = 1, 2, 4, 8
+# o3v_decode_state.flags (values 1 and 2 are retired): O3V_DECODE_NO_QKV_FUSED_NORM (switches a form OFF), O3V_DECODE_KV8_EMULATE
+# (tests: the fp8 K/V arithmetic on a bf16 cache)
+DECODE_NO_QKV_FUSED_NORM, DECODE_KV8_EMULATE = 4, 8
 DECODE_RAGGED = 16              # O3V_DECODE_RAGGED: the state is a DecodeStateRagged
 
 _lib = None

@@ -48,10 +48,9 @@ __device__ __forceinline__ float wave_max(float v) {
     return v;
 }
 
-// ---- RMSNorm of ONE row by ONE wave (TF:65-79): out = w * bf16(x * rsqrt(mean(x^2) + eps)); the row is held in VGPRs.  Shared by
-// rmsnorm_kernel (o3v_elem.hip) and by the finishing waves of the residual linears that normalise for the next linear
-// (o3v_gemm.hip, TailNorm), so both round identically: chunks lane + 64 i ascending in one fmaf chain, then the wave butterfly.
-// ld_chunk(c) returns the c-th 16-byte chunk of the row (a plain or an L1-bypassing load).
+// ---- RMSNorm of ONE row by ONE wave (TF:65-79): out = w * bf16(x * rsqrt(mean(x^2) + eps)); the row is held in VGPRs.  The body of
+// rmsnorm_kernel (o3v_elem.hip): chunks lane + 64 i ascending in one fmaf chain, then the wave butterfly.
+// ld_chunk(c) returns the c-th 16-byte chunk of the row.
 template <int MAXCH, class LoadChunk>
 __device__ __forceinline__ void rmsnorm_row_wave(LoadChunk ld_chunk, const bf16_t* __restrict__ w, bf16_t* __restrict__ orow_, int cols,
                                                  float eps) {

@@ -397,9 +397,7 @@ extern "C" int o3v_llm_prefill_ex(const o3v_llm_desc* d, void* x, const void* co
 namespace {
 // what the decode linears stream: bf16, fp8 rows (<= 3 rows), fp8 fragments (4..32 rows); the MLP alone: MXFP4 rows / fragments
 enum Weights { W_BF16, W_FP8_ROWS, W_FP8_FRAGS, W_MXFP4_ROWS, W_MXFP4_FRAGS };
-// pre_normed: `normed` already holds RMSNorm(x; final_norm) (the last down_proj of a batched decode step normalised it, TailNorm)
-int llm_head(const o3v_llm_desc* d, const void* x, int ldx, int rows, void* normed, void* logits, Weights wf, o3v_stream_t s,
-             bool pre_normed = false) {
+int llm_head(const o3v_llm_desc* d, const void* x, int ldx, int rows, void* normed, void* logits, Weights wf, o3v_stream_t s) {
     if (!d || !x || !normed || !logits || rows <= 0) return O3V_ERR_ARG;
     const int H = d->hidden;
     if (wf == W_FP8_FRAGS && rows >= 4 && rows <= 32 && d->lm_head8p) {  // batched decode on fp8 rows: norm apart, fp8 fragments widened in registers
@@ -408,7 +406,7 @@ int llm_head(const o3v_llm_desc* d, const void* x, int ldx, int rows, void* norm
                                           O3V_EPI_NONE, s);
     }
     if (rows >= 8 && rows <= 32 && d->lm_head_p) {  // batched decode: norm apart, LDS-free matrix-core linear
-        if (!pre_normed) TRY(o3v_rmsnorm(x, d->final_norm, normed, rows, H, ldx, H, d->rms_eps, s));
+        TRY(o3v_rmsnorm(x, d->final_norm, normed, rows, H, ldx, H, d->rms_eps, s));
         return o3v_linear_decode(normed, nullptr, 0.f, d->lm_head, d->lm_head_p, nullptr, nullptr, logits, rows, d->vocab, H, H,
                                  d->vocab, 0, O3V_EPI_NONE, s);
     }
@@ -427,7 +425,7 @@ int llm_head(const o3v_llm_desc* d, const void* x, int ldx, int rows, void* norm
 // rows are DECODE rows (o3v_llm_decode streams them), a log-prob must not depend on how many rows its chunk happens to hold
 extern "C" int o3v_llm_head(const o3v_llm_desc* d, const void* x, int ldx, int rows, void* normed, void* logits,
                             o3v_stream_t s) {
-    return llm_head(d, x, ldx, rows, normed, logits, W_BF16, s, false);
+    return llm_head(d, x, ldx, rows, normed, logits, W_BF16, s);
 }
 
 // o3v_sample.hip: the sampler of one step followed by its log-probs
@@ -456,11 +454,11 @@ struct Regime {
     bool kv8, kv8_emulate;                            // fp8 K/V cache; its arithmetic emulated on a bf16 cache (tests)
     bool ragged;                                      // a context per row (row_base): staging rows, o3v_attn_decode_ragged
     const int* own_lo;                                // group rows with left-padded suffixes in their own caches: the gap mask, else NULL
-    bool block, layer_block, tail;                    // tried, may fall back: see settle()
+    bool block;                                       // tried, may fall back: see settle()
 };
-// The one rule of the try-then-fall-back forms: O3V_ERR_SHAPE from the FIRST launch of a form in a call (layer 0 of its first step)
-// switches the form off for the rest of the call; any other non-OK code, and O3V_ERR_SHAPE later on, is returned.  Every such condition
-// of o3v_decode_attn_block*, o3v_decode_layer_block and o3v_linear_decode_norm_next is a constant of the call (shapes, device, residency).
+// The one-launch attention block is tried and may fall back: O3V_ERR_SHAPE from its FIRST launch in a call (layer 0 of the first step)
+// switches it off for the rest of the call; any other non-OK code, and O3V_ERR_SHAPE later on, is returned.  Every such condition of
+// o3v_decode_attn_block* is a constant of the call (shapes, device, residency).
 int settle(bool& on, bool first, int rc) {
     if (rc != O3V_ERR_SHAPE || !first) return rc;
     on = false;
@@ -498,28 +496,23 @@ Regime decide_regime(const o3v_llm_desc* d, const o3v_decode_state* st) {
     r.group = st->group > 1;           // the rows of a group share the prompt K/V: read it once per group
     // batch 1: q/k/v + attention + merge + o_proj as ONE launch (o3v_fused.hip); epoch = index of the launch in this generate call
     r.block = st->sync && B == 1 && st->group <= 1 && st->nsplit > 0;
-    // the persistent layer block (attention half + gate/up in one launch): bf16 rows, no q/k norm
-    r.layer_block = r.block && (st->flags & O3V_DECODE_LAYER_BLOCK) && !fp8 && !r.qk_norm;
-    // 8..32 bf16 rows: the residual linears normalise for the linear that follows (o3v_linear_decode_norm_next), so only layer 0's
-    // first norm of a step is a launch of its own.  O3V_DECODE_NO_TAIL_NORM switches it off (A/B, tests).
-    r.tail = r.norm_apart && !fp8b && st->sync && !(st->flags & O3V_DECODE_NO_TAIL_NORM) && d->lm_head_p && l0.o_wp && l0.down_wp;
     // fp8 K/V (independent rows only; o3v_llm_decode_ex refuses it for groups): q/k/v writes the new token's bf16 K/V rows into one
     // layer's worth of staging rows, the attention kernel quantises them into the cache -- stand-alone launches, no one-launch form.
     // The emulation (tests) round-trips the new token's row of an ordinary bf16 cache after q/k/v instead.
     r.kv8 = st->k8 != nullptr;
     r.kv8_emulate = !r.kv8 && (st->flags & O3V_DECODE_KV8_EMULATE);
-    if (r.kv8 || r.kv8_emulate) r.block = r.layer_block = false;
+    if (r.kv8 || r.kv8_emulate) r.block = false;
     // ragged rows (continuous batching; the three fields exist only behind O3V_DECODE_RAGGED): q/k/v writes the staging rows as under
     // kv8, the attention kernel appends them at each row's own slot -- stand-alone launches
     r.ragged = (st->flags & O3V_DECODE_RAGGED) && st->row_base != nullptr;
-    if (r.ragged) r.block = r.layer_block = false;
+    if (r.ragged) r.block = false;
     // suffixes behind a shared prefix (o3v_llm_decode_ex has checked that this is a group on a prompt entry): the group kernels mask
     // each row's padding slots; NULL launches the kernels of before
     r.own_lo = r.group ? st->own_lo : nullptr;
     return r;
 }
 
-// One decode call: its regime, what its step functions share (workspace, dimensions, strides, the running step) and the hand-overs
+// One decode call: its regime and what its step functions share (workspace, dimensions, strides, the running step)
 struct Decode {
     const o3v_llm_desc* d;
     const o3v_decode_state* st;
@@ -532,20 +525,14 @@ struct Decode {
     LlmWs w;
     float scale;
     size_t layer_stride, pre_stride;
-    // The "already normalised" hand-overs of a forward (TailNorm).  Whatever rewrites x (a new token's embedding, a residual linear)
-    // calls x_changed(); the o3v_linear_decode_norm_next launch that did it then sets the one it wrote.
-    bool h_ready;       // w.h holds RMSNorm(x; ln1 of the layer about to run)
-    bool h2_ready;      // w.h holds RMSNorm(x; ln2 of the running layer)
-    bool normed_ready;  // w.normed holds RMSNorm(x; final_norm)
-    void x_changed() { h_ready = h2_ready = normed_ready = false; }
     // where q/k/v appends the new token's K/V: slot slot0 + step of layer l's cache; fp8 K/V: the staging rows [B][Hkv][1][D]
     // ragged rows: the staging rows kstage / vstage likewise
     char* kc(int l) const { return r.ragged ? (char*)st->kstage : (char*)st->kcache + (r.kv8 ? 0 : l * layer_stride); }
     char* vc(int l) const { return r.ragged ? (char*)st->vstage : (char*)st->vcache + (r.kv8 ? 0 : l * layer_stride); }
     int kv_slot() const { return r.kv8 || r.ragged ? 0 : slot0 + step; }
     int kv_cap() const { return r.kv8 || r.ragged ? 1 : st->Tmax; }
-    uint32_t epoch(int l) const { return (uint32_t)(step * d->layers + l + 1); }  // of the one-launch forms
-    bool first(int l) const { return l == 0 && step == step0; }                   // the launch at which settle() may switch a form off
+    uint32_t epoch(int l) const { return (uint32_t)(step * d->layers + l + 1); }  // of the one-launch block
+    bool first(int l) const { return l == 0 && step == step0; }                   // the launch at which settle() may switch it off
     int sample(const o3v_logprob_opts* lp, const o3v_sampling_opts* so, const o3v_guided_opts* go) {
         // so: the extended sampler kernels on this step's controls, then (lp given) its log-probs
         // lp alone: the same sampler, then the log-probs of what it drew (sampling: the embedding row is gathered below as usual)
@@ -589,9 +576,9 @@ struct Decode {
     // q/k/v (+norm, rope, cache append) of layer l
     int qkv(int l, const o3v_llm_layer_w& lw) {
         const Weights wf = r.qkv_weights;
-        // the norm in front as a launch of its own: always on fp8 fragments; on bf16 rows where norms run apart, unless handed over
+        // the norm in front as a launch of its own: always on fp8 fragments; on bf16 rows where norms run apart
         const bool apart = wf == W_FP8_FRAGS || (r.norm_apart && !r.qkv_fused_norm);
-        if (apart && (wf == W_FP8_FRAGS || !h_ready)) TRY(o3v_rmsnorm(st->x, lw.ln1, w.h, B, H, H, H, d->rms_eps, s));
+        if (apart) TRY(o3v_rmsnorm(st->x, lw.ln1, w.h, B, H, H, H, d->rms_eps, s));
         const void *xin = apart ? w.h : st->x, *ln = apart ? nullptr : lw.ln1;  // normalised x, or x and the norm to fuse
         if (r.qk_norm) {
             TRY(lin(wf, xin, ln, lw.qkv_w, lw.qkv_wp, lw.qkv_w8, lw.qkv_w8p, lw.qkv_s, lw.qkv_b, w.qkv, NQKV, H, NQKV, O3V_EPI_NONE));
@@ -628,21 +615,14 @@ struct Decode {
         return o3v_attn_decode(w.q, kc(l), vc(l), w.att, st->part_o, st->part_ml, st->k_lo, B, Hq, Hkv, D, st->S + step + 1, st->Tmax,
                                st->nsplit, scale, s);
     }
-    // o_proj + residual of layer l (TailNorm: and the norm in front of gate/up)
-    int o_proj(int l, const o3v_llm_layer_w& lw) {
-        x_changed();
-        if (r.tail) {
-            const uint32_t ep = (uint32_t)(step * d->layers + l) * 2u + 1u;
-            TRY(settle(r.tail, first(l), o3v_linear_decode_norm_next(w.att, lw.o_wp, st->x, st->x, B, H, QD, QD, H, H, lw.ln2, d->rms_eps, w.h, H,
-                                                                     st->sync, ep, s)));
-            if ((h2_ready = r.tail)) return O3V_OK;  // else not this device / these shapes: two launches, for the whole call
-        }
+    // o_proj + residual
+    int o_proj(const o3v_llm_layer_w& lw) {
         return lin(r.weights, w.att, nullptr, lw.o_w, lw.o_wp, lw.o_w8, lw.o_w8p, lw.o_s, nullptr, st->x, H, QD, H, O3V_EPI_RESIDUAL);
     }
-    // MLP half of layer l: (norm,) gate/up + SwiGLU, down_proj + residual (TailNorm: and the norm in front of the next linear)
-    int mlp(int l, const o3v_llm_layer_w& lw) {
-        const bool frags = r.weights == W_FP8_FRAGS, apart = frags || r.norm_apart;
-        if (apart && (frags || !h2_ready)) TRY(o3v_rmsnorm(st->x, lw.ln2, w.h, B, H, H, H, d->rms_eps, s));
+    // MLP half of a layer: (norm,) gate/up + SwiGLU, down_proj + residual
+    int mlp(const o3v_llm_layer_w& lw) {
+        const bool apart = r.weights == W_FP8_FRAGS || r.norm_apart;
+        if (apart) TRY(o3v_rmsnorm(st->x, lw.ln2, w.h, B, H, H, H, d->rms_eps, s));
         const void *xin = apart ? w.h : st->x, *ln = apart ? nullptr : lw.ln2;
         if (r.mlp_weights == W_MXFP4_ROWS)
             TRY(lin4(W_MXFP4_ROWS, xin, ln, lw.gu_w4, lw.gu_s4, w.mlp, 2 * I, H, I, O3V_EPI_SWIGLU));
@@ -650,18 +630,9 @@ struct Decode {
             TRY(lin4(W_MXFP4_FRAGS, xin, ln, lw.gu_w4p, lw.gu_s4p, w.mlp, 2 * I, H, I, O3V_EPI_SWIGLU));
         else
             TRY(lin(r.weights, xin, ln, lw.gu_w, lw.gu_wp, lw.gu_w8, lw.gu_w8p, lw.gu_s, nullptr, w.mlp, 2 * I, H, I, O3V_EPI_SWIGLU));
-        return down_proj(l, lw);
+        return down_proj(lw);
     }
-    int down_proj(int l, const o3v_llm_layer_w& lw) {  // also behind the layer block
-        x_changed();
-        if (r.tail) {  // down_proj + the next layer's first norm (the head's norm after the last layer)
-            const bool last = l + 1 == d->layers;
-            const uint32_t ep = (uint32_t)(step * d->layers + l) * 2u + 2u;
-            TRY(o3v_linear_decode_norm_next(w.mlp, lw.down_wp, st->x, st->x, B, H, I, I, H, H, last ? d->final_norm : d->layer[l + 1].ln1,
-                                            d->rms_eps, last ? w.normed : w.h, H, st->sync, ep, s));
-            (last ? normed_ready : h_ready) = true;
-            return O3V_OK;
-        }
+    int down_proj(const o3v_llm_layer_w& lw) {
         if (r.mlp_weights == W_MXFP4_ROWS) return lin4(W_MXFP4_ROWS, w.mlp, nullptr, lw.down_w4, lw.down_s4, st->x, H, I, H, O3V_EPI_RESIDUAL);
         if (r.mlp_weights == W_MXFP4_FRAGS) return lin4(W_MXFP4_FRAGS, w.mlp, nullptr, lw.down_w4p, lw.down_s4p, st->x, H, I, H, O3V_EPI_RESIDUAL);
         return lin(r.weights, w.mlp, nullptr, lw.down_w, lw.down_wp, lw.down_w8, lw.down_w8p, lw.down_s, nullptr, st->x, H, I, H,
@@ -688,25 +659,15 @@ struct Decode {
         if (!r.block) {
             TRY(qkv(l, lw));
             TRY(attention(l));
-            TRY(o_proj(l, lw));
+            TRY(o_proj(lw));
         }
         if (hs) ++hs[r.block ? 2 : 3];
         return O3V_OK;
     }
     int layer(int l) {
         const o3v_llm_layer_w& lw = d->layer[l];
-        if (r.layer_block) {
-            TRY(settle(r.layer_block, first(l),
-                       o3v_decode_layer_block(st->x, lw.ln1, d->rms_eps, lw.qkv_w, lw.qkv_b, lw.o_w, lw.ln2, lw.gu_w, w.mlp, st->cosT,
-                                              st->sinT, w.q, w.att, kc(l), vc(l), st->part_o, st->part_ml, st->k_lo, H, I, Hq, Hkv, D,
-                                              st->S + step, st->Tmax, st->Tnew, step, st->nsplit, scale, st->sync, epoch(l), s)));
-            if (r.layer_block) {
-                if (hs) ++hs[2];
-                return down_proj(l, lw);
-            }  // off: shapes or residency: the role-per-workgroup block (or the stand-alone kernels) instead
-        }
         TRY(attention_half(l, lw));
-        return mlp(l, lw);
+        return mlp(lw);
     }
 };
 }  // namespace
@@ -756,7 +717,6 @@ extern "C" int o3v_llm_decode_guided(const o3v_llm_desc* d, const o3v_decode_sta
         if (!ragged && c.slot0 + c.step >= st->Tmax) return O3V_ERR_ARG;
         // one decode forward: token `step` sits in cache slot S+step, context = S+step+1 keys
         if (st->do_sample) TRY(o3v_embed_tokens(d->embed, st->cur_tok, st->x, B, c.H, s));
-        c.x_changed();  // x is the sampler's embedding row
         const long long launches0 = o3v_tl_launches;
         for (int l = 0; l < d->layers; ++l) TRY(c.layer(l));
         if (c.hs) {
@@ -764,7 +724,7 @@ extern "C" int o3v_llm_decode_guided(const o3v_llm_desc* d, const o3v_decode_sta
             c.hs[1] += o3v_tl_launches - launches0;
         }
         // the head follows the layers: fp8 rows only when the layer stack of this call streams fp8 rows
-        TRY(llm_head(d, st->x, c.H, B, c.w.normed, st->logits, c.r.weights, s, c.normed_ready));
+        TRY(llm_head(d, st->x, c.H, B, c.w.normed, st->logits, c.r.weights, s));
     }
     return O3V_OK;
 }

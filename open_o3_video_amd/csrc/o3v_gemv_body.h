@@ -238,7 +238,7 @@ __device__ __forceinline__ void gemv_body(const bf16_t* __restrict__ X, const bf
         // ascending, one fmaf chain each), 4 virtual waves of 64 (the wave_sum butterfly), their sums added 0..3.  Real wave w
         // plays the virtual waves w, w + NW, ... -- with 4 waves exactly its own, with fewer several, waves past the fourth
         // none.  So rstd, and with it every normalised element, does not depend on the decomposition the launcher picked
-        // (or on which kernel -- stand-alone, one-launch block, norm_finish of the layer block -- computes it).
+        // (or on which kernel -- stand-alone or one-launch block -- computes it).
         constexpr int VW = (4 + NW - 1) / NW;        // virtual waves per real wave (at most)
         constexpr bool ALLV = (4 % NW) == 0;         // 1, 2, 4 waves: every (wave, v) is one of the four virtual waves
         constexpr int XC = 2;                        // chunks per virtual thread kept in registers (K <= 4096)

@@ -72,7 +72,7 @@ class DecodePlan(NamedTuple):
 
 
 def plan_decode(num_attention_heads: int, num_key_value_heads: int, head_dim: int, B0: int, G: int, S: int, T: int,
-                group_attention: bool = True, group_attention_mode: str = "auto", fused: bool = True, tail_norm: bool = False,
+                group_attention: bool = True, group_attention_mode: str = "auto", fused: bool = True,
                 nsplit_override: Optional[int] = None, suffix: int = 0) -> DecodePlan:
     """The decode attention plan of a generate call: B0 prompts of S slots, G completions each, T new tokens.  Pure arithmetic on
     the model's head geometry and the engine's switches (`fused`: the one-launch decode forms are allowed in this call;
@@ -116,9 +116,8 @@ def plan_decode(num_attention_heads: int, num_key_value_heads: int, head_dim: in
                 nsplit = max(1, min(64 - own_splits, (S + 127) // 128))
         else:
             nsplit = -nsplit
-    # tickets / mailboxes of the one-launch attention block (batch 1); 8..32 rows: the residual linears of the batched decode
-    # normalise for the next linear through the same buffer
-    want_sync = bool(fused and (B == 1 or (B >= 8 and tail_norm)))
+    # tickets / mailboxes of the one-launch attention block (batch 1 only)
+    want_sync = bool(fused and B == 1)
     return DecodePlan(B, own_splits, bool(shared_prompt), Tmax, nsplit, group, want_sync)
 
 
@@ -288,8 +287,7 @@ class _DecodeBuffers:
         # decode forwards, launches in their layer loops, fused / stand-alone attention halves
         self.host_stats = (C.c_longlong * 4)(0, 0, 0, 0)
         self.st.host_stats = C.cast(self.host_stats, C.c_void_p)
-        self.st.flags = ((_lib.DECODE_LAYER_BLOCK if eng.layer_block else 0) | (0 if eng.tail_norm else _lib.DECODE_NO_TAIL_NORM) |
-                         (0 if eng.qkv_fused_norm else _lib.DECODE_NO_QKV_FUSED_NORM) | (_lib.DECODE_KV8_EMULATE if kv8_emulate else 0))
+        self.st.flags = (0 if eng.qkv_fused_norm else _lib.DECODE_NO_QKV_FUSED_NORM) | (_lib.DECODE_KV8_EMULATE if kv8_emulate else 0)
         if kv8 is not None:
             self.st.k8, self.st.v8, self.st.k8s, self.st.v8s = (t.data_ptr() for t in kv8)
         self.row_base = self.stage = None
@@ -344,15 +342,6 @@ class O3VEngine:
         self.group_attention = os.environ.get("O3V_GROUP_ATTENTION", "1") != "0"   # A/B switch for the shared-prefix kernel
         self.fused_decode = os.environ.get("O3V_FUSED_DECODE", "1") != "0"         # A/B switch for the one-launch attention block
         self.group_attention_mode = os.environ.get("O3V_GROUP_MODE", "auto")
-        # the persistent layer block (o3v_decode_layer_block: attention half + gate/up as one launch of resident, row-pipelined
-        # workgroups) is bit-identical but measured SLOWER than the role block + gate/up launch (95.3 vs 90.3 us per layer at 7B,
-        # profiles/r03_layer_block_timeline_v2.txt): off unless O3V_LAYER_BLOCK=1
-        self.layer_block = os.environ.get("O3V_LAYER_BLOCK", "0") == "1"
-        # 8..32 decode rows: o_proj / down_proj can also normalise their result for the linear that follows (o3v_linear_decode_norm_next,
-        # bit-identical to the separate o3v_rmsnorm launch it replaces).  Measured equal, not faster (G=8 3.765 vs 3.760 ms/step, G=16
-        # 4.324 vs 4.321: the in-launch chain store-ack -> ticket -> poll -> row load costs the residual linear +6.4 us, the launch it
-        # removes 5.9 us; profiles/r03_tail_norm_ab.txt): off unless O3V_TAIL_NORM=1
-        self.tail_norm = os.environ.get("O3V_TAIL_NORM", "0") == "1"
         self.qkv_fused_norm = os.environ.get("O3V_QKV_FUSED_NORM", "1") != "0"     # A/B switch for the norm fused into q/k/v at 8 rows
         # video rope arithmetic (indexing.rope_index): "tf5" = transformers 5.15 (goldens G5b / G14 / G15), "pinned" = the
         # libraries the reference installs (transformers @336dc69d, vllm 0.7.2).  The facades choose; images do not depend on it.
@@ -748,10 +737,9 @@ class O3VEngine:
         def make_plan(fused):
             if P:   # the B0 rows as one group behind one prefix of P tokens
                 return plan_decode(tc.num_attention_heads, tc.num_key_value_heads, tc.head_dim, 1, B0, P, T, self.group_attention,
-                                   self.group_attention_mode, fused, self.tail_norm, int(nsplit_env) if nsplit_env else None,
-                                   suffix=Lmax)
+                                   self.group_attention_mode, fused, int(nsplit_env) if nsplit_env else None, suffix=Lmax)
             return plan_decode(tc.num_attention_heads, tc.num_key_value_heads, tc.head_dim, B0, G, S, T, self.group_attention,
-                               self.group_attention_mode, fused, self.tail_norm, int(nsplit_env) if nsplit_env else None)
+                               self.group_attention_mode, fused, int(nsplit_env) if nsplit_env else None)
 
         plan = make_plan(self.fused_decode and _fused_ok)
         replicate = False

@@ -1322,160 +1322,54 @@ def test_decode_attn_block_fp8_equals_three_launches(dev, Hq, Hkv, H, ctx, Tmax,
         assert torch.equal(att2.view(torch.int16), att1.view(torch.int16)) and torch.equal(x2.view(torch.int16), x1.view(torch.int16))
 
 
-@pytest.mark.parametrize("Hq,Hkv,H,I,ctx,Tmax,nsplit,pad", [
-    (28, 4, 3584, 18944, 4491, 5002, 37, 0),     # 7B, first decode step of the bench prompt
-    (28, 4, 3584, 18944, 5002, 5002, 40, 37),    # last slot of the cache, left-padded prompt
-    (16, 2, 2048, 11008, 1500, 1732, 14, 0),     # 3B dims (n_rep 8)
-    (16, 2, 2048, 11008, 40, 64, 1, 0),          # 3B dims, one split
-    (28, 4, 3584, 18944, 97, 20480, 64, 3),      # few keys against 64 splits: most attention items hold no key at all
-    (28, 4, 3584, 18944, 1, 64, 1, 0),           # one key (the token itself)
-])
-def test_decode_layer_block_equals_stand_alone_launches(dev, Hq, Hkv, H, I, ctx, Tmax, nsplit, pad):
-    """o3v_decode_layer_block (ONE persistent launch: q/k/v -> attention -> merge -> o_proj -> RMSNorm -> gate/up + SwiGLU, every wave
-    streaming its own weight rows across the in-launch hand-offs) == o3v_gemv_norm_qkv_rope + o3v_attn_decode + o3v_linear_decode(o_proj,
-    RESIDUAL) + o3v_linear_decode(gate/up, fused RMSNorm, SWIGLU) BIT FOR BIT: residual stream, q, attention output, the appended K/V
-    row, the SwiGLU vector.  Three epochs on one sync buffer with new inputs each time."""
-    import ctypes as C
-    from open_o3_video_amd import _lib
-    from open_o3_video_amd.weights import pack_gate_up
-    D, Tnew, step = 128, 7, 3
-    slot = ctx - 1
-    g = torch.Generator().manual_seed(Hq * 1000 + ctx + I)
-    N, QD = (Hq + 2 * Hkv) * D, Hq * D
-    nw1 = (1 + 0.1 * torch.randn(H, generator=g)).to(BF).to(dev)
-    nw2 = (1 + 0.1 * torch.randn(H, generator=g)).to(BF).to(dev)
-    wqkv = (torch.randn(N, H, generator=g) / math.sqrt(H)).to(BF).to(dev)
-    bqkv = (0.5 * torch.randn(N, generator=g)).to(BF).to(dev)
-    wo = (torch.randn(H, QD, generator=g) / math.sqrt(QD)).to(BF).to(dev)
-    wgu = pack_gate_up((torch.randn(I, H, generator=g) / math.sqrt(H)).to(BF), (torch.randn(I, H, generator=g) / math.sqrt(H)).to(BF), I).to(dev)
-    ang = torch.rand(1, Tnew, D // 2, generator=g) * 30
-    cos = torch.cat([ang.cos(), ang.cos()], -1).to(BF).to(dev).contiguous()
-    sin = torch.cat([ang.sin(), ang.sin()], -1).to(BF).to(dev).contiguous()
-    kc0 = torch.randn(1, Hkv, Tmax, D, generator=g).to(BF).to(dev)
-    vc0 = torch.randn(1, Hkv, Tmax, D, generator=g).to(BF).to(dev)
-    kc0[:, :, slot] = float("nan")
-    vc0[:, :, slot] = float("nan")
-    nan_fill_(kc0[:, :, ctx:])
-    nan_fill_(vc0[:, :, ctx:])
-    k_lo = torch.tensor([pad], dtype=torch.int32, device=dev)
-    P = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-    scale = 1.0 / math.sqrt(D)
-    lib = _lib.load()
-    sync = torch.zeros(lib.o3v_decode_sync_bytes(), dtype=torch.uint8, device=dev)
-    part_o = torch.empty(Hq * 64 * D, dtype=torch.float32, device=dev)
-    part_ml = torch.empty(Hq * 64 * 2, dtype=torch.float32, device=dev)
-    q2, att2 = torch.zeros(1, Hq, D, dtype=BF, device=dev), torch.zeros(1, Hq, D, dtype=BF, device=dev)
-    k2, v2 = kc0.clone(), vc0.clone()
-    act2 = torch.zeros(1, I, dtype=BF, device=dev)
-    for rep in range(3):
-        x0 = (torch.randn(1, H, generator=g) * 2).to(BF).to(dev)
-        x1 = x0.clone()
-        q1 = torch.zeros(1, Hq, D, dtype=BF, device=dev)
-        k1, v1 = kc0.clone(), vc0.clone()
-        att1 = torch.zeros(1, Hq, D, dtype=BF, device=dev)
-        act1 = torch.zeros(1, I, dtype=BF, device=dev)
-        po1, pm1 = torch.empty_like(part_o), torch.empty_like(part_ml)
-        _lib.call("o3v_gemv_norm_qkv_rope", P(x1), P(nw1), 1e-6, P(wqkv), None, P(bqkv), 1, H, H, P(cos), P(sin), P(q1), P(k1), P(v1),
-                  slot, Hq, Hkv, D, Tmax, Tnew, step, st)
-        _lib.call("o3v_attn_decode", P(q1), P(k1), P(v1), P(att1), P(po1), P(pm1), P(k_lo), 1, Hq, Hkv, D, ctx, Tmax, nsplit, scale, st)
-        _lib.call("o3v_linear_decode", P(att1), None, 0.0, P(wo), None, None, P(x1), P(x1), 1, H, QD, QD, H, H, _lib.EPI_RESIDUAL, st)
-        _lib.call("o3v_linear_decode", P(x1), P(nw2), 1e-6, P(wgu), None, None, None, P(act1), 1, 2 * I, H, H, I, 0, _lib.EPI_SWIGLU, st)
-        x2 = x0.clone()
-        k2[:, :, slot] = float("nan")
-        v2[:, :, slot] = float("nan")
-        act2.zero_()
-        rc = lib.o3v_decode_layer_block(P(x2), P(nw1), 1e-6, P(wqkv), P(bqkv), P(wo), P(nw2), P(wgu), P(act2), P(cos), P(sin), P(q2), P(att2),
-                                        P(k2), P(v2), P(part_o), P(part_ml), P(k_lo), H, I, Hq, Hkv, D, slot, Tmax, Tnew, step, nsplit, scale,
-                                        P(sync), rep + 1, st)
-        assert rc == 0, rc
-        torch.cuda.synchronize()
-        tmo = int(sync[_lib.SYNC_TMO_BYTE:_lib.SYNC_TMO_BYTE + 4].view(torch.int32)[0].item())
-        assert tmo == 0, f"an in-launch wait timed out (code {tmo:#x})"
-        assert not torch.isnan(x1.float()).any() and not torch.isnan(act1.float()).any()
-        assert torch.equal(q2.view(torch.int16), q1.view(torch.int16))
-        assert torch.equal(k2.view(torch.int16), k1.view(torch.int16)) and torch.equal(v2.view(torch.int16), v1.view(torch.int16))
-        assert torch.equal(att2.view(torch.int16), att1.view(torch.int16))
-        assert torch.equal(x2.view(torch.int16), x1.view(torch.int16))
-        assert torch.equal(act2.view(torch.int16), act1.view(torch.int16))
-
-
 def test_fused_rmsnorm_does_not_depend_on_the_decomposition(dev):
     """The RMSNorm prologue of the weight-streaming GEMV adds the squares in one order whatever workgroup size the launcher picks
     (o3v_gemv_body.h: 256 virtual threads, 4 virtual waves): the same weight rows give the same bits through a 6144-row call (3 waves
-    per workgroup at K = 4096), a 2048-row call (4 waves) and the gate/up form of a 2-wave workgroup is covered by the layer-block
-    test.  x has a wide dynamic range so that the order of the additions matters; before the order was fixed the one-launch attention
-    block (4 waves) and the stand-alone q/k/v launch (3 waves) differed about once in 500 layer evaluations."""
+    per workgroup at K = 4096) and a 2048-row call (4 waves), and the same (gate, up) rows through the gate/up form of a 2-wave
+    workgroup (I = 8192 columns: launch_gemv_m's `outs >= 8192`) and of a 4-wave one (I = 2048), both one pair per wave and no K
+    split, at K = 4096 and 3584.  x has a wide dynamic range so that the order of the additions matters; before the order was fixed
+    the one-launch attention block (4 waves) and the stand-alone q/k/v launch (3 waves) differed about once in 500 layer evaluations."""
     import ctypes as C
     from open_o3_video_amd import _lib
+    from open_o3_video_amd.weights import pack_gate_up
     K, N1, N2 = 4096, 6144, 2048
+    I1, I2 = 8192, 2048
     g = torch.Generator().manual_seed(77)
     w = (torch.randn(N1, K, generator=g) / math.sqrt(K)).to(BF).to(dev)
     nw = (1 + 0.1 * torch.randn(K, generator=g)).to(BF).to(dev)
     P = lambda t: None if t is None else C.c_void_p(t.data_ptr())
     st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    g2 = torch.Generator().manual_seed(78)   # gate / up: a stream of their own, the x rows below stay those of generator g
+
+    def gate_up(k):
+        gate = (torch.randn(I1, k, generator=g2) / math.sqrt(k)).to(BF)
+        up = (torch.randn(I1, k, generator=g2) / math.sqrt(k)).to(BF)
+        return pack_gate_up(gate, up, I1).to(dev), pack_gate_up(gate[:I2], up[:I2], I2).to(dev)
+
+    def swiglu_two_and_four_waves(x, nwk, gu1, gu2, k, trial):
+        a1 = torch.zeros(1, I1, dtype=BF, device=dev)
+        a2 = torch.zeros(1, I2, dtype=BF, device=dev)
+        _lib.call("o3v_linear_decode", P(x), P(nwk), 1e-6, P(gu1), None, None, None, P(a1), 1, 2 * I1, k, k, I1, 0, _lib.EPI_SWIGLU, st)
+        _lib.call("o3v_linear_decode", P(x), P(nwk), 1e-6, P(gu2), None, None, None, P(a2), 1, 2 * I2, k, k, I2, 0, _lib.EPI_SWIGLU, st)
+        assert torch.equal(a1[:, :I2].view(torch.int16), a2.view(torch.int16)), (k, trial)
+
+    gu1, gu2 = gate_up(K)
+    xs = []
     for trial in range(96):
         x = (torch.randn(1, K, generator=g) * torch.exp(1.5 * torch.randn(1, K, generator=g))).to(BF).to(dev)
+        xs.append(x)
         o1 = torch.zeros(1, N1, dtype=BF, device=dev)
         o2 = torch.zeros(1, N2, dtype=BF, device=dev)
         _lib.call("o3v_linear_decode", P(x), P(nw), 1e-6, P(w), None, None, None, P(o1), 1, N1, K, K, N1, 0, _lib.EPI_NONE, st)
         _lib.call("o3v_linear_decode", P(x), P(nw), 1e-6, P(w), None, None, None, P(o2), 1, N2, K, K, N2, 0, _lib.EPI_NONE, st)
         assert torch.equal(o1[:, :N2].view(torch.int16), o2.view(torch.int16)), trial
-
-
-@pytest.mark.parametrize("M", [8, 11, 16, 24, 32])
-@pytest.mark.parametrize("N,K", [(3584, 3584), (3584, 18944), (2048, 11008), (4096, 12288), (896, 4864)])
-def test_linear_decode_norm_next_equals_linear_plus_rmsnorm(dev, M, N, K):
-    """o3v_linear_decode_norm_next (residual linear whose last M storing waves normalise one row each for the NEXT linear) ==
-    o3v_linear_decode(RESIDUAL) + o3v_rmsnorm BIT FOR BIT, residual stream in place, four epochs on one sync buffer, no wait
-    gave up.  Shapes: o_proj / down_proj of the 7B, 3B and 8B classes and of the medium fixture."""
-    import ctypes as C
-    from open_o3_video_amd import _lib
-    from open_o3_video_amd.weights import pack_mfma_fragments
-    g = torch.Generator().manual_seed(N + K + M)
-    w = (torch.randn(N, K, generator=g) / math.sqrt(K)).to(BF).to(dev)
-    wp = pack_mfma_fragments(w)
-    nw = (1 + 0.1 * torch.randn(N, generator=g)).to(BF).to(dev)
-    lib = _lib.load()
-    sync = torch.zeros(lib.o3v_decode_sync_bytes(), dtype=torch.uint8, device=dev)
-    P = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-    h2 = torch.zeros(M, N, dtype=BF, device=dev)
-    for epoch in range(1, 5):
-        a = torch.randn(M, K, generator=g).to(BF).to(dev)
-        x0 = (torch.randn(M, N, generator=g) * 2).to(BF).to(dev)
-        x1, x2 = x0.clone(), x0.clone()
-        h1 = torch.zeros(M, N, dtype=BF, device=dev)
-        _lib.call("o3v_linear_decode", P(a), None, 0.0, P(w), P(wp), None, P(x1), P(x1), M, N, K, K, N, N, _lib.EPI_RESIDUAL, st)
-        _lib.call("o3v_rmsnorm", P(x1), P(nw), P(h1), M, N, N, N, 1e-6, st)
-        h2.fill_(float("nan"))
-        rc = lib.o3v_linear_decode_norm_next(P(a), P(wp), P(x2), P(x2), M, N, K, K, N, N, P(nw), 1e-6, P(h2), N, P(sync), epoch, st)
-        assert rc == 0, rc
-        torch.cuda.synchronize()
-        tmo = int(sync[_lib.SYNC_TMO_BYTE:_lib.SYNC_TMO_BYTE + 4].view(torch.int32)[0].item())
-        assert tmo == 0, f"a wait gave up (code {tmo:#x})"
-        assert torch.equal(x2.view(torch.int16), x1.view(torch.int16))
-        assert torch.equal(h2.view(torch.int16), h1.view(torch.int16)), (epoch, (h2.float() - h1.float()).abs().max().item())
-
-
-def test_linear_decode_norm_next_rejects(dev):
-    """Shapes the form does not take return O3V_ERR_SHAPE / O3V_ERR_ARG before any launch (the engine then issues two launches)."""
-    import ctypes as C
-    from open_o3_video_amd import _lib
-    lib = _lib.load()
-    t = torch.zeros(32 * 8192, dtype=BF, device=dev)
-    sync = torch.zeros(lib.o3v_decode_sync_bytes(), dtype=torch.uint8, device=dev)
-    P = lambda x: C.c_void_p(x.data_ptr())
-    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-    call = lambda M, N, K, ep, sy: lib.o3v_linear_decode_norm_next(P(t), P(t), P(t), P(t), M, N, K, K, N, N, P(t), 1e-6, P(t), N, sy, ep, st)
-    assert call(4, 3584, 3584, 1, P(sync)) == _lib.ERR_SHAPE          # fewer than 8 rows: the fused-norm linears
-    assert call(33, 3584, 3584, 1, P(sync)) == _lib.ERR_SHAPE
-    assert call(8, 8192, 1024, 1, P(sync)) == _lib.ERR_SHAPE          # rows longer than a wave normalises from registers
-    assert call(16, 128, 1024, 1, P(sync)) == _lib.ERR_SHAPE          # fewer storing waves than rows
-    assert call(8, 3584, 3584, 0, P(sync)) == _lib.ERR_ARG            # epochs start at 1
-    assert call(8, 3584, 3584, 1, None) == _lib.ERR_ARG
-    torch.cuda.synchronize()
-    assert int(sync.view(torch.int32).abs().sum().item()) == 0
+        swiglu_two_and_four_waves(x, nw, gu1, gu2, K, trial)
+    del gu1, gu2
+    K2 = 3584   # the 7B hidden size: the norm's second chunk per virtual thread is partly past the row
+    gu1, gu2 = gate_up(K2)
+    nw2 = (1 + 0.1 * torch.randn(K2, generator=g2)).to(BF).to(dev)
+    for trial in range(96):   # the same 96 rows, cut to K2 columns
+        swiglu_two_and_four_waves(xs[trial][:, :K2].contiguous(), nw2, gu1, gu2, K2, trial)
 
 
 @pytest.mark.parametrize("M,N,K", [(256, 256, 256), (700, 1280, 384), (515, 3456, 1280), (1030, 520, 256), (300, 4608, 3584),

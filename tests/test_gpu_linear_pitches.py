@@ -81,15 +81,13 @@ class Spec:
     ref(t) reference check of the contiguous run                         expect the documented status
     alias  (input, output): that input is updated in place -- one buffer at the output's pitch
     dense  name -> (shape, dtype): outputs without a pitch (q, the K/V cache), canary-filled in both runs and compared bit for bit
-    prepare(t) adds per-run scratch (a zeroed sync buffer); after(t) checks it and the dense outputs of a call that ran,
-    refused(t) checks it after a call that was refused
+    after(t) checks the dense outputs of a call that ran
     expect_canvas: the documented status of the canvas call where it differs from the contiguous one's (a pitch the header rules
     out: the contiguous call, whose pitches are the widths, still runs)"""
 
-    def __init__(self, call, ins, outs, ref=None, expect=OK, alias=None, dense=None, prepare=None, after=None, refused=None,
-                 expect_canvas=None):
+    def __init__(self, call, ins, outs, ref=None, expect=OK, alias=None, dense=None, after=None, expect_canvas=None):
         self.call, self.ins, self.outs, self.ref, self.expect, self.alias = call, ins, outs, ref, expect, alias
-        self.dense, self.prepare, self.after, self.refused = dense or {}, prepare, after, refused
+        self.dense, self.after = dense or {}, after
         self.expect_canvas = expect if expect_canvas is None else expect_canvas
 
 
@@ -97,8 +95,6 @@ def _dense(spec, t, dev):
     for name, (shape, dt) in spec.dense.items():
         t[name] = torch.empty(shape, dtype=dt, device=dev)
         raw(t[name]).fill_(CANARY16 if dt == BF else ops.CANARY & 0xFF)
-    if spec.prepare:
-        spec.prepare(t)
 
 
 def run(dev, spec):
@@ -120,8 +116,6 @@ def run(dev, spec):
             spec.after(t1)
         if spec.ref:
             spec.ref(t1)
-    elif spec.refused:
-        spec.refused(t1)
     expect = spec.expect_canvas
     # ---- the same values on canvases
     widest = max([p for _, p in spec.ins.values()] + [o[2] for o in spec.outs.values()])
@@ -160,8 +154,6 @@ def run(dev, spec):
             assert (raw(t2[name]) == (CANARY16 if t2[name].dtype == BF else ops.CANARY & 0xFF)).all(), f"{name} written by a refused call"
     if expect == OK and spec.after:
         spec.after(t2)
-    if expect != OK and spec.refused:
-        spec.refused(t2)
 
 
 # ------------------------------------------------------------------------------------------------ operands, shared by the cases of a shape
@@ -311,44 +303,6 @@ def decode_spec(entry, M, N, K, epi, ldo, ldr=0, norm=False, bias=True, inplace=
                 close_bf16(out, g, ulps=1, atol=2e-3, frac=0.999)
 
     return Spec(call, ins, {"out": (M, No, ldo, BF)}, ref, alias=("res", "out") if inplace else None)
-
-
-def norm_next_spec(M, N, K, inplace):
-    """o3v_linear_decode_norm_next == o3v_linear_decode(RESIDUAL) + o3v_rmsnorm bit for bit (the check of
-    test_linear_decode_norm_next_equals_linear_plus_rmsnorm); ldx, ldo, ldh padded to different multiples of 8, ldr odd (any pitch),
-    a freshly zeroed sync buffer at epoch 1 whose time-out word stays 0.  The form needs M storing waves, one per 16 columns of N:
-    32 rows x 256 columns are refused with O3V_ERR_SHAPE, nothing written, the sync buffer still zero."""
-    from open_o3_video_amd import _lib
-    from open_o3_video_amd.weights import pack_mfma_fragments
-    if "gfx950" not in torch.cuda.get_device_properties(0).gcnArchName:
-        pytest.skip("o3v_linear_decode_norm_next is offered on gfx950 only")
-    d = _lin(M, N, K)
-    wp = pack_mfma_fragments(d["w"])
-    ins = {"x": (d["x"], K + 8), "res": (d["res"], N + 8 if inplace else N + 5)}
-
-    def prepare(t):
-        t["sync"] = torch.zeros(lib().o3v_decode_sync_bytes(), dtype=U8, device="cuda")
-
-    def call(t):
-        x, res, out, h = t["x"], t["res"], t["out"], t["h"]
-        return lib().o3v_linear_decode_norm_next(P(x), P(wp), P(res), P(out), M, N, K, ld(x), ld(out), ld(res), P(d["nw_out"]), 1e-6, P(h),
-                                                 ld(h), P(t["sync"]), 1, st())
-
-    def after(t):
-        tmo = int(t["sync"][_lib.SYNC_TMO_BYTE:_lib.SYNC_TMO_BYTE + 4].view(torch.int32)[0].item())
-        assert tmo == 0, f"a wait gave up (code {tmo:#x})"
-
-    def ref(t):
-        x1 = d["res"].clone()
-        _lib.call("o3v_linear_decode", P(d["x"]), None, 0.0, P(d["w"]), P(wp), None, P(x1), P(x1), M, N, K, K, N, N, ops.EPI_RESIDUAL, st())
-        h1 = ops.rmsnorm(x1, d["nw_out"], 1e-6)
-        assert torch.equal(raw(t["out"]), raw(x1)) and torch.equal(raw(t["h"]), raw(h1))
-
-    def refused(t):
-        assert int(t["sync"].view(torch.int32).abs().sum().item()) == 0, "a refused call touched the sync buffer"
-
-    return Spec(call, ins, {"out": (M, N, N + 8, BF), "h": (M, N, N + 24, BF)}, ref, alias=("res", "out") if inplace else None,
-                prepare=prepare, after=after, refused=refused, expect=ERR_SHAPE if N // 16 < M else OK)
 
 
 def bad_pitch_spec(make, name, pitch, code, *a, **kw):
@@ -609,11 +563,6 @@ for _entry in ("gemv", "decode"):
             for _ldo in (_N // 2 + 8, _N // 2 + 1):
                 add(decode_spec, _entry, _M, _N, _K, "swiglu", _ldo)
 
-# 32 rows run the two-column-block kernel; at N = 256 there are 16 storing waves: 32 rows are refused (documented O3V_ERR_SHAPE)
-for _M, _N, _K in ((8, 256, 256), (32, 512, 256), (32, 256, 256)):
-    for _inplace in (False, True):
-        add(norm_next_spec, _M, _N, _K, _inplace)
-
 # fp8 / MXFP4 decode linears at the smallest legal (N, K); N = 197 where the header allows it (the row forms)
 for _entry, _Ms in (("fp8", (1, 2, 3)), ("mxfp4", (1, 2, 3)), ("fp8_rows", (4, 21)), ("mxfp4_rows", (4, 21))):
     for _M in _Ms:
@@ -656,8 +605,6 @@ add(bad_pitch_spec, decode_spec, "w", 136 + 4, ERR_SHAPE, "gemv", 3, 197, 136, "
 add(bad_pitch_spec, decode_spec, "x", 160 + 4, ERR_SHAPE, "decode", 9, 208, 160, "none", 216)
 for _entry, _M in (("fp8", 2), ("mxfp4", 2), ("fp8_rows", 4), ("mxfp4_rows", 4)):
     add(bad_pitch_spec, decode_spec, "x", 128 + 4, ERR_SHAPE, _entry, _M, 48, 128, "none", 56)
-for _name, _pitch in (("x", 256 + 4), ("out", 256 + 4), ("h", 256 + 12)):
-    add(bad_pitch_spec, norm_next_spec, _name, _pitch, ERR_SHAPE, 8, 256, 256, False)
 add(bad_pitch_spec, qkv_spec, "x", 128 + 4, ERR_SHAPE, "bf16", 1)
 add(bad_pitch_spec, qkv_spec, "x", 128 + 4, ERR_SHAPE, "fp8_rows", 9)
 add(bad_pitch_spec, w8a8_spec, "a8", 256 + 8, ERR_SHAPE, 1, 130, 200, 256, "none", 208)

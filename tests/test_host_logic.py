@@ -718,57 +718,41 @@ PLAN_TABLE = [
     ((28, 4, 128, 1, 4, 4500, 256), dict(group_attention=False), (4, 2, False, 4756, 38, 0, False)),
     ((28, 4, 128, 1, 4, 4500, 256), dict(nsplit_override=7), (4, 2, True, 256, -7, 4, False)),
     ((28, 4, 128, 1, 4, 4500, 256), dict(fused=False), (4, 2, True, 256, -38, 4, False)),
-    ((28, 4, 128, 1, 4, 4500, 256), dict(tail_norm=True), (4, 2, True, 256, -38, 4, False)),
-    ((28, 4, 128, 1, 4, 4500, 256), dict(fused=False, tail_norm=True), (4, 2, True, 256, -38, 4, False)),
     ((28, 4, 128, 1, 4, 10000, 256), dict(group_attention_mode='kernel'), (4, 2, True, 256, 62, 4, False)),
     ((28, 4, 128, 1, 4, 10000, 256), dict(group_attention_mode='shared_read'), (4, 2, True, 256, -40, 4, False)),
     ((28, 4, 128, 1, 4, 10000, 256), dict(group_attention=False), (4, 2, False, 10256, 40, 0, False)),
     ((28, 4, 128, 1, 4, 10000, 256), dict(nsplit_override=7), (4, 2, True, 256, 62, 4, False)),
     ((28, 4, 128, 1, 4, 10000, 256), dict(fused=False), (4, 2, True, 256, 62, 4, False)),
-    ((28, 4, 128, 1, 4, 10000, 256), dict(tail_norm=True), (4, 2, True, 256, 62, 4, False)),
-    ((28, 4, 128, 1, 4, 10000, 256), dict(fused=False, tail_norm=True), (4, 2, True, 256, 62, 4, False)),
     ((28, 4, 128, 1, 8, 4500, 256), dict(group_attention_mode='kernel'), (8, 2, True, 256, 36, 4, False)),
     ((28, 4, 128, 1, 8, 4500, 256), dict(group_attention_mode='shared_read'), (8, 2, True, 256, -20, 8, False)),
     ((28, 4, 128, 1, 8, 4500, 256), dict(group_attention=False), (8, 2, False, 4756, 20, 0, False)),
     ((28, 4, 128, 1, 8, 4500, 256), dict(nsplit_override=7), (8, 2, True, 256, -7, 8, False)),
     ((28, 4, 128, 1, 8, 4500, 256), dict(fused=False), (8, 2, True, 256, -20, 8, False)),
-    ((28, 4, 128, 1, 8, 4500, 256), dict(tail_norm=True), (8, 2, True, 256, -20, 8, True)),
-    ((28, 4, 128, 1, 8, 4500, 256), dict(fused=False, tail_norm=True), (8, 2, True, 256, -20, 8, False)),
     ((28, 4, 128, 1, 8, 10000, 256), dict(group_attention_mode='kernel'), (8, 2, True, 256, 62, 4, False)),
     ((28, 4, 128, 1, 8, 10000, 256), dict(group_attention_mode='shared_read'), (8, 2, True, 256, -20, 8, False)),
     ((28, 4, 128, 1, 8, 10000, 256), dict(group_attention=False), (8, 2, False, 10256, 20, 0, False)),
     ((28, 4, 128, 1, 8, 10000, 256), dict(nsplit_override=7), (8, 2, True, 256, 62, 4, False)),
     ((28, 4, 128, 1, 8, 10000, 256), dict(fused=False), (8, 2, True, 256, 62, 4, False)),
-    ((28, 4, 128, 1, 8, 10000, 256), dict(tail_norm=True), (8, 2, True, 256, 62, 4, True)),
-    ((28, 4, 128, 1, 8, 10000, 256), dict(fused=False, tail_norm=True), (8, 2, True, 256, 62, 4, False)),
     ((28, 4, 128, 1, 16, 4500, 256), dict(group_attention_mode='kernel'), (16, 2, True, 256, 20, 4, False)),
     ((28, 4, 128, 1, 16, 4500, 256), dict(group_attention_mode='shared_read'), (16, 2, True, 256, -10, 16, False)),
     ((28, 4, 128, 1, 16, 4500, 256), dict(group_attention=False), (16, 2, False, 4756, 10, 0, False)),
     ((28, 4, 128, 1, 16, 4500, 256), dict(nsplit_override=7), (16, 2, True, 256, 20, 4, False)),
     ((28, 4, 128, 1, 16, 4500, 256), dict(fused=False), (16, 2, True, 256, 20, 4, False)),
-    ((28, 4, 128, 1, 16, 4500, 256), dict(tail_norm=True), (16, 2, True, 256, 20, 4, True)),
-    ((28, 4, 128, 1, 16, 4500, 256), dict(fused=False, tail_norm=True), (16, 2, True, 256, 20, 4, False)),
     ((28, 4, 128, 1, 16, 10000, 256), dict(group_attention_mode='kernel'), (16, 2, True, 256, 62, 4, False)),
     ((28, 4, 128, 1, 16, 10000, 256), dict(group_attention_mode='shared_read'), (16, 2, True, 256, -10, 16, False)),
     ((28, 4, 128, 1, 16, 10000, 256), dict(group_attention=False), (16, 2, False, 10256, 10, 0, False)),
     ((28, 4, 128, 1, 16, 10000, 256), dict(nsplit_override=7), (16, 2, True, 256, 62, 4, False)),
     ((28, 4, 128, 1, 16, 10000, 256), dict(fused=False), (16, 2, True, 256, 62, 4, False)),
-    ((28, 4, 128, 1, 16, 10000, 256), dict(tail_norm=True), (16, 2, True, 256, 62, 4, True)),
-    ((28, 4, 128, 1, 16, 10000, 256), dict(fused=False, tail_norm=True), (16, 2, True, 256, 62, 4, False)),
     ((28, 4, 128, 8, 1, 4500, 256), dict(group_attention_mode='kernel'), (8, 2, False, 4756, 20, 0, False)),
     ((28, 4, 128, 8, 1, 4500, 256), dict(group_attention_mode='shared_read'), (8, 2, False, 4756, 20, 0, False)),
     ((28, 4, 128, 8, 1, 4500, 256), dict(group_attention=False), (8, 2, False, 4756, 20, 0, False)),
     ((28, 4, 128, 8, 1, 4500, 256), dict(nsplit_override=7), (8, 2, False, 4756, 7, 0, False)),
     ((28, 4, 128, 8, 1, 4500, 256), dict(fused=False), (8, 2, False, 4756, 20, 0, False)),
-    ((28, 4, 128, 8, 1, 4500, 256), dict(tail_norm=True), (8, 2, False, 4756, 20, 0, True)),
-    ((28, 4, 128, 8, 1, 4500, 256), dict(fused=False, tail_norm=True), (8, 2, False, 4756, 20, 0, False)),
     ((28, 4, 128, 8, 1, 10000, 256), dict(group_attention_mode='kernel'), (8, 2, False, 10256, 20, 0, False)),
     ((28, 4, 128, 8, 1, 10000, 256), dict(group_attention_mode='shared_read'), (8, 2, False, 10256, 20, 0, False)),
     ((28, 4, 128, 8, 1, 10000, 256), dict(group_attention=False), (8, 2, False, 10256, 20, 0, False)),
     ((28, 4, 128, 8, 1, 10000, 256), dict(nsplit_override=7), (8, 2, False, 10256, 7, 0, False)),
     ((28, 4, 128, 8, 1, 10000, 256), dict(fused=False), (8, 2, False, 10256, 20, 0, False)),
-    ((28, 4, 128, 8, 1, 10000, 256), dict(tail_norm=True), (8, 2, False, 10256, 20, 0, True)),
-    ((28, 4, 128, 8, 1, 10000, 256), dict(fused=False, tail_norm=True), (8, 2, False, 10256, 20, 0, False)),
     ((16, 2, 128, 1, 1, 4500, 256), dict(fused=False), (1, 2, False, 4756, 38, 0, False)),
     ((16, 2, 128, 1, 16, 10000, 256), dict(group_attention_mode='kernel', nsplit_override=7), (16, 2, True, 256, 62, 4, False)),
 ]
@@ -779,7 +763,7 @@ def test_plan_decode_matches_the_recorded_table():
     their sign, group size, hand-off buffer) against rows recorded from the in-line arithmetic it replaces: the 7B / 3B /
     Qwen3-VL-8B / head_dim-64 geometries x every (B0, G) shape, the S and T edges (127..129 keys, the 8192 kernel threshold,
     T = 4097 -> 33 own splits -> no shared prompt), the three group modes, group attention off, an O3V_NSPLIT override (applied
-    before the group branch: the kernel mode recomputes it, shared-read negates it), and fused / tail_norm on and off."""
+    before the group branch: the kernel mode recomputes it, shared-read negates it), and fused on and off."""
     from open_o3_video_amd.engine import DecodePlan, plan_decode
     assert DecodePlan._fields == ("B", "own_splits", "shared_prompt", "Tmax", "nsplit", "group", "want_sync")
     for args, kw, want in PLAN_TABLE:
